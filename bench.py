@@ -444,6 +444,26 @@ def other_workload(args) -> None:
         dist.destroy_process_group()
 
 
+DUMP_MAX_ELEMS = 1 << 21     # per array: 4 stems x 8 MB of float32, within a 64 MB budget
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Write each device tensor as out_dir/<name>.npy in float32.  A tensor of more than DUMP_MAX_ELEMS values is sampled: the
+    flattened tensor is cut into DUMP_MAX_ELEMS equal strides and one position per stride is drawn from a generator seeded with
+    the array's index, so the positions depend only on the shape and two builds run with the same arguments compare value for value."""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, (name, t) in enumerate(arrays.items()):
+        flat = t.detach()
+        n = flat.numel()
+        if n > DUMP_MAX_ELEMS:
+            flat = flat.reshape(-1)
+            stride = n // DUMP_MAX_ELEMS
+            rng = np.random.default_rng(k)
+            idx = np.arange(DUMP_MAX_ELEMS, dtype=np.int64) * stride + rng.integers(0, stride, DUMP_MAX_ELEMS)
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), flat.float().cpu().numpy())
+
+
 def _bench_cfg():
     from audiolab_amd.tdfnet import TDFNetConfig
     return TDFNetConfig()
@@ -473,8 +493,15 @@ def main() -> None:
                          "configs[2] (htdemucs 6-stem, segments sharded over the ranks), tracks = configs[3] (batch of tracks per GPU, MDX "
                          "ensemble + htdemucs, replicas), longform = configs[4] (48 kHz 8-channel, Hann overlap-add at 0.75, chunks sharded)")
     ap.add_argument("--tracks", type=int, default=8, help="tracks per GPU of the tracks workload")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the stems of the last timed step as DIR/stem<i>.npy (float32; at most "
+                         f"{DUMP_MAX_ELEMS} values per stem: longer stems are sampled at fixed, seeded positions, see dump_outputs())")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     if args.workload != "mdx4":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: only the mdx4 workload writes its outputs")
         return other_workload(args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -560,6 +587,8 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t[0])
     assert stems[0].shape == (1, 2, n_samples) and bool(torch.isfinite(stems[0]).all())
+    if args.dump_outputs and rank == 0:                     # before any untimed pass below can reuse a buffer
+        dump_outputs(args.dump_outputs, {f"stem{i}": s for i, s in enumerate(stems)})
     # the other scaling mode, after the timed region (N > 1 only; at N = 1 the two coincide): same models, the other track length
     other_scaling = None
     if world > 1:
