@@ -631,6 +631,71 @@ demucs_mix_out_kernel(const float* __restrict__ xt, const float* __restrict__ st
     }
 }
 
+// Bag of Demucs models, last step (demucs.apply.apply_model over a BagOfModels + DemucsSeparator's de-normalisation), one pass over
+// the weighted overlap-add sums of every view (= one shift pass of one member):
+//   out[s, c, t] = mean + std * sum_v coef[v, s] * q_v(row[v, s] * 2 + c, t + cut[v]),   row[v, s] < 0: view v does not carry s
+//   q_v(r, x)    = wsum_v[x] != 0 ? acc_v[r * ld_v + x] / wsum_v[x] : 0                    (as nn_vec_div_kernel)
+// Memory-bound: each thread owns kBagPerThread samples of ALL S x 2 outputs, 256 consecutive t per load across the workgroup (dword loads:
+// a view's cut leaves its rows unaligned), so wsum_v is read once per view and every carried row once; no LDS.  32-bit t within a row.
+constexpr int kBagMaxS = 8;
+constexpr int kBagMaxViews = 64;
+constexpr int kBagPerThread = 4;
+__global__ void __launch_bounds__(kNnThreads)
+demucs_bag_finish_kernel(const float* const* __restrict__ acc, const float* const* __restrict__ wsum, const int64_t* __restrict__ ld,
+                         const int32_t* __restrict__ cut, const int32_t* __restrict__ row, const float* __restrict__ coef,
+                         const float* __restrict__ stats, float* __restrict__ out, int V, int S, int L) {
+    const int t0 = (int)blockIdx.x * (kNnThreads * kBagPerThread) + (int)threadIdx.x;
+    float o[kBagMaxS][2][kBagPerThread];
+#pragma unroll
+    for (int s = 0; s < kBagMaxS; ++s)
+#pragma unroll
+        for (int k = 0; k < kBagPerThread; ++k) o[s][0][k] = o[s][1][k] = 0.f;
+    for (int v = 0; v < V; ++v) {
+        const int cv = cut[v];
+        const float* wv = wsum[v] + cv;
+        const float* av = acc[v] + cv;
+        const int64_t ldv = ld[v];
+        float w[kBagPerThread];
+#pragma unroll
+        for (int k = 0; k < kBagPerThread; ++k) {
+            const int t = t0 + k * kNnThreads;
+            w[k] = t < L ? wv[t] : 0.f;
+        }
+#pragma unroll
+        for (int s = 0; s < kBagMaxS; ++s) {
+            if (s >= S) break;
+            const int r = row[v * S + s];
+            if (r < 0) continue;
+            const float cf = coef[v * S + s];
+            const float* a0 = av + (int64_t)(2 * r) * ldv;
+            const float* a1 = a0 + ldv;
+#pragma unroll
+            for (int k = 0; k < kBagPerThread; ++k) {
+                const int t = t0 + k * kNnThreads;
+                if (t < L && w[k] != 0.f) {
+                    o[s][0][k] = fmaf(cf, a0[t] / w[k], o[s][0][k]);
+                    o[s][1][k] = fmaf(cf, a1[t] / w[k], o[s][1][k]);
+                }
+            }
+        }
+    }
+    const float mean = stats[0], sd = stats[1];
+#pragma unroll
+    for (int s = 0; s < kBagMaxS; ++s) {
+        if (s >= S) break;
+        float* y0 = out + (int64_t)(2 * s) * L;
+        float* y1 = y0 + L;
+#pragma unroll
+        for (int k = 0; k < kBagPerThread; ++k) {
+            const int t = t0 + k * kNnThreads;
+            if (t < L) {
+                y0[t] = fmaf(o[s][0][k], sd, mean);
+                y1[t] = fmaf(o[s][1][k], sd, mean);
+            }
+        }
+    }
+}
+
 // y [B, L, C] = x [B, C, L]  (and back with the roles of L and C swapped)
 __global__ void __launch_bounds__(kNnThreads)
 nn_swap_last2_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n, int64_t C, int64_t L) {
@@ -1365,6 +1430,20 @@ extern "C" int alsep_demucs_mix_out(alsep_ctx* ctx, const float* xt, const float
     const int64_t n = B * S * 2 * L;
     hipLaunchKernelGGL(demucs_mix_out_kernel, dim3(ew_grid(n)), dim3(kNnThreads), 0, ctx->stream, xt, statst, xs, out, n, S, L);
     ALSEP_LAUNCH_CHECK(ctx, "demucs_mix_out_kernel");
+    return ALSEP_OK;
+}
+
+extern "C" int alsep_demucs_bag_finish(alsep_ctx* ctx, const float* const* acc, const float* const* wsum, const int64_t* ld,
+                                       const int32_t* cut, const int32_t* row, const float* coef, const float* stats, float* out, int V,
+                                       int S, int64_t L) {
+    ALSEP_ENTER(ctx);
+    NN_ARG(ctx && acc && wsum && ld && cut && row && coef && stats && out && V > 0 && V <= kBagMaxViews && S > 0 && S <= kBagMaxS &&
+               L > 0 && L <= INT32_MAX - kNnThreads * kBagPerThread,
+           "alsep_demucs_bag_finish");
+    const int64_t blocks = ceil_div64(L, kNnThreads * kBagPerThread);
+    hipLaunchKernelGGL(demucs_bag_finish_kernel, dim3((unsigned)blocks), dim3(kNnThreads), 0, ctx->stream, acc, wsum, ld, cut, row, coef,
+                       stats, out, V, S, (int)L);
+    ALSEP_LAUNCH_CHECK(ctx, "demucs_bag_finish_kernel");
     return ALSEP_OK;
 }
 

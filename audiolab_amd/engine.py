@@ -14,6 +14,11 @@ hyper-parameters -- or, only with ``allow_synthetic=True`` (bench / tests), from
 shapes against the configuration and names the mismatching hyper-parameter.  Geometry per file name follows the public UVR / KUIELab /
 training-project tables (PARITY UNPINNED: upstream, uncited).
 
+Demucs.  ``htdemucs_6s.yaml`` (the orchestrator's multi-stem stage), ``htdemucs.yaml`` (one 4-source HTDemucs) and ``htdemucs_ft.yaml`` (a
+bag of four 4-source HTDemucs with demucs' per-source weights) load from the yaml and the ``.th`` packages it names; every member of a bag
+is read (a missing one is an error) and the members must agree on sources, samplerate and channels.  ``hdemucs_mmi.yaml`` (an HDemucs
+package) is not implemented.
+
 Multi-stem entries.  A roster value ``("multi", [(label, cfg), ...])`` describes an MDX-Net style file set that yields several stems: one
 network per label.
 
@@ -58,6 +63,7 @@ def _cfg(n_fft: int, dim_f: int, dim_t: int) -> TDFNetConfig:
     return TDFNetConfig(dim_f=dim_f, dim_t=dim_t, n_fft=n_fft, g=48)
 
 
+_DEMUCS4 = ("drums", "bass", "other", "vocals")
 MODEL_ROSTER: Dict[str, tuple] = {
     # UVR MDX-Net vocal models (ensemble slots 5-7, stem_separator.py:384-386): n_fft 7680, dim_f 3072, dim_t 2**8
     "UVR-MDX-NET-Voc_FT.onnx": ("Vocals", "Instrumental", _cfg(7680, 3072, 256), {"compensate": 1.021}),
@@ -104,6 +110,13 @@ MODEL_ROSTER: Dict[str, tuple] = {
     "UVR-De-Echo-Aggressive.pth": ("vr", dict(arch="new", params="4band_v3", nout=48, nout_lstm=128), {"labels": ("No Echo", "Echo")}),
     # the multi-stem stage (stem_separator.py:466): HTDemucs 6 sources on the full mix; DemucsSeparator defaults shifts 2, overlap 0.25
     "htdemucs_6s.yaml": ("demucs", HTDemucsConfig(), {"shifts": 2, "overlap": 0.25}),
+    # the other HTDemucs names the reference downloads (stem_separator.py:110): htdemucs = one 4-source network; htdemucs_ft = a bag of
+    # four 4-source networks with the identity weight matrix (one specialist per source) -- the layouts as published with demucs 4,
+    # recalled (upstream, uncited -- PARITY UNPINNED).  "members" / "weights" only shape the synthetic bag of allow_synthetic; a real
+    # yaml names its own members and weights.
+    "htdemucs.yaml": ("demucs", HTDemucsConfig(sources=_DEMUCS4), {"shifts": 2, "overlap": 0.25}),
+    "htdemucs_ft.yaml": ("demucs", HTDemucsConfig(sources=_DEMUCS4),
+                         {"shifts": 2, "overlap": 0.25, "members": 4, "weights": [[1.0 if i == j else 0.0 for j in range(4)] for i in range(4)]}),
 }
 # BASELINE configs[1] "MDX-Net UVR 4-stem": four single-target networks of the in-tree geometry (mdxnet.py:247-251:
 # dim_f 3072, n_fft 6144) -- the bench workload; never reached by a file name of the reference
@@ -163,7 +176,7 @@ class _ModelInstance:
         self.output_dir = None
         self.model_run = net                                  # callable(spek) -> pred, the patch_separate seam
         self.extra: List[tuple] = []                          # multi-stem models: further (label, net, predictor)
-        self.demucs: Optional[DemucsRunner] = None            # Demucs-family model: one network, all sources at once
+        self.demucs: Optional[DemucsRunner] = None            # Demucs-family model (or bag of models): all sources at once
         self.roformer: Optional[RoformerRunner] = None        # Roformer-family model: its own chunked runner
         self.vr = None                                        # VR-architecture model: vr_frontend.VRSeparator
 
@@ -310,44 +323,73 @@ class Separator:
         self.model_instance = inst
 
     def _load_demucs(self, model_filename: str, entry: tuple) -> None:
-        """("demucs", HTDemucsConfig, {shifts, overlap}).  Weights, in this order: the files the reference has -- ``<dir>/<name>.yaml``
-        (demucs' bag-of-models list) pointing at ``<signature>-<checksum>.th`` (a pickled package: read by audiolab_amd.th_reader's
-        allow-list unpickler, hyper-parameters from its ``kwargs``, ``state`` as the weights); ``<dir>/<name>.pt`` (a plain state_dict with
-        demucs' parameter names); with allow_synthetic, seeded random-init ones.  float32 (the kernels of this family are fp32)."""
+        """("demucs", HTDemucsConfig, {shifts, overlap[, members, weights]}).  Weights, in this order: the files the reference has --
+        ``<dir>/<name>.yaml`` (demucs' bag-of-models list, audiolab_amd.th_reader.resolve_demucs_bag) pointing at one
+        ``<signature>-<checksum>.th`` per member (a pickled package: read by th_reader's allow-list unpickler, hyper-parameters from its
+        ``kwargs``, ``state`` as the weights); ``<dir>/<name>.pt`` (a plain state_dict with demucs' parameter names; single models only);
+        with allow_synthetic, seeded random-init ones (a bag entry: ``members`` networks seeded from ``<name>#<i>``, the entry's ``weights``).
+        A yaml of several models gives a bag (one network per member, all read -- a member file missing is an error, never a synthetic
+        stand-in); the members must agree on sources, samplerate and channels.  float32 (the kernels of this family are fp32)."""
         from . import th_reader
         cfg = entry[1]
         opts = entry[2] if len(entry) > 2 else {}
+        n_members = int(opts.get("members", 1))
         pt = os.path.join(self.model_file_dir, model_filename + ".pt")
-        th_path = th_reader.resolve_demucs_yaml(self.model_file_dir, model_filename) if model_filename.endswith(".yaml") else None
+        bag = th_reader.resolve_demucs_bag(self.model_file_dir, model_filename) if model_filename.endswith(".yaml") else None
+        th_path = bag[0][0] if bag is not None and len(bag[0]) == 1 else None
         if th_path is None and model_filename.endswith(".th") and os.path.isfile(os.path.join(self.model_file_dir, model_filename)):
             th_path = os.path.join(self.model_file_dir, model_filename)
-        sd = None
-        if th_path is not None:
+        sd, members, bag_weights = None, None, None             # members: [(HTDemucsConfig, state_dict)] of a bag of several models
+        if bag is not None and len(bag[0]) > 1:
+            members = []
+            for path in bag[0]:
+                pkg = th_reader.read_th(path)
+                if pkg["klass"] != "HTDemucs":
+                    raise AlsepError(f"{path}: a {pkg['klass']} package -- only HTDemucs is implemented")
+                members.append((th_reader.htdemucs_config_from_kwargs(pkg["kwargs"]), pkg["state"]))
+            c0 = members[0][0]
+            for path, (ci, _) in zip(bag[0][1:], members[1:]):
+                if (ci.sources, ci.samplerate, ci.audio_channels) != (c0.sources, c0.samplerate, c0.audio_channels):
+                    raise AlsepError(f"{path}: sources / samplerate / audio_channels {ci.sources} / {ci.samplerate} / {ci.audio_channels} "
+                                     f"differ from the bag's first member ({c0.sources} / {c0.samplerate} / {c0.audio_channels})")
+            bag_weights = th_reader.bag_weights(bag[1], len(members), c0.S, os.path.join(self.model_file_dir, model_filename))
+            weights = "real"
+        elif th_path is not None:
             pkg = th_reader.read_th(th_path)
             if pkg["klass"] != "HTDemucs":
                 raise AlsepError(f"{th_path}: a {pkg['klass']} package -- only HTDemucs is implemented")
             cfg = th_reader.htdemucs_config_from_kwargs(pkg["kwargs"])
             sd, weights = pkg["state"], "real"
-        else:
+        elif n_members == 1:
             sd = self._weights_file(model_filename) if not model_filename.endswith(".yaml") else None
             if sd is None and os.path.isfile(pt):
                 sd = torch.load(pt, map_location="cpu", weights_only=True)
                 sd = sd.get("state", sd) if isinstance(sd, dict) and isinstance(sd.get("state"), dict) else sd
-        if sd is not None:
-            weights = "real"
-        elif self.allow_synthetic:
+        if members is None and sd is None:
+            if not self.allow_synthetic:
+                raise AlsepError(f"model '{model_filename}': no weight file ({os.path.join(self.model_file_dir, model_filename)} naming a .th "
+                                 f"package, or {pt}); random-init weights are only used with Separator(allow_synthetic=True)")
             from .htdemucs import synthetic_state_dict as demucs_synth
-            seed = int.from_bytes(hashlib.sha256(model_filename.encode()).digest()[:4], "little")
-            sd, weights = demucs_synth(cfg, seed=seed), "synthetic"
+            if n_members == 1:
+                seed = int.from_bytes(hashlib.sha256(model_filename.encode()).digest()[:4], "little")
+                sd, weights = demucs_synth(cfg, seed=seed), "synthetic"
+            else:
+                members = [(cfg, demucs_synth(cfg, seed=int.from_bytes(hashlib.sha256(f"{model_filename}#{i}".encode()).digest()[:4], "little")))
+                           for i in range(n_members)]
+                bag_weights, weights = opts.get("weights"), "synthetic"
             logger.warning("%s: no weight file under %s -- SYNTHETIC random-init weights (allow_synthetic=True)", model_filename,
                            self.model_file_dir)
+        elif sd is not None:
+            weights = "real"
+        if members is not None:
+            nets = [HTDemucs(c, sd_i, ctx=self.ctx) for c, sd_i in members]
+            net, cfg = nets[0], nets[0].cfg
         else:
-            raise AlsepError(f"model '{model_filename}': no weight file ({os.path.join(self.model_file_dir, model_filename)} naming a .th "
-                             f"package, or {pt}); random-init weights are only used with Separator(allow_synthetic=True)")
-        net = HTDemucs(cfg, sd, ctx=self.ctx)
+            net = HTDemucs(cfg, sd, ctx=self.ctx)
+            nets = net
         inst = _ModelInstance(model_filename, net, None, cfg.sources[0].capitalize(), None)
-        inst.demucs = DemucsRunner(net, shifts=int(opts.get("shifts", 2)), overlap=float(opts.get("overlap", 0.25)), sharded=self.sharded,
-                                   contraction=self.nn_contraction)
+        inst.demucs = DemucsRunner(nets, shifts=int(opts.get("shifts", 2)), overlap=float(opts.get("overlap", 0.25)), sharded=self.sharded,
+                                   contraction=self.nn_contraction, weights=bag_weights)
         inst.output_dir = self.output_dir
         inst.weights = weights
         self._cache[model_filename] = inst

@@ -19,6 +19,12 @@ Runner: ``demucs.apply.apply_model`` (shifts, split into 7.8 s segments every 75
 ``DemucsSeparator``'s whole-track normalisation.  demucs draws the shift offsets with ``random.randint`` per call; this build
 fixes them with a seeded generator.  With ``sharded=True`` the (shift, segment) units are split over the ranks of a
 ``torch.distributed`` group and the weighted partial sums are exchanged once (audiolab_amd.dist).
+
+Bags of models (``htdemucs_ft.yaml``: four networks, one per source): the runner takes a list of member networks and demucs' per-source
+weight matrix.  A *view* is one shift pass of one member (its network, offset, segment geometry, summed window weights and accumulator of
+the sources that member weighs); the unit list, the lanes and the sharded seam logic run over views.  A bag of several members is
+finished by ONE kernel (``alsep_demucs_bag_finish``: divide, cut, weigh per source, add, de-normalise); a single model keeps its
+per-pass finish.
 """
 from __future__ import annotations
 
@@ -522,16 +528,47 @@ def shift_offsets(shifts: int, max_shift: int, seed: int = 0) -> List[int]:
     return [int(torch.randint(0, max_shift + 1, (1,), generator=g)) for _ in range(shifts)]
 
 
+class _View:
+    """one shift pass of one bag member: its network, offset, segment geometry, carried sources and their contiguous runs
+    [(first source, sources in the run, first accumulator row pair)]"""
+
+    def __init__(self, m: int, offset: int, view_len: int, seg: int, stride: int, rows: List[int]):
+        self.m, self.offset, self.view_len, self.seg, self.stride, self.rows = m, offset, view_len, seg, stride, rows
+        self.runs: List[Tuple[int, int, int]] = []
+        for j, s in enumerate(rows):
+            if self.runs and self.runs[-1][0] + self.runs[-1][1] == s:
+                s0, n, j0 = self.runs[-1]
+                self.runs[-1] = (s0, n + 1, j0)
+            else:
+                self.runs.append((s, 1, j))
+
+
 class DemucsRunner:
     """``demucs.apply.apply_model(model, mix, shifts, split=True, overlap)`` inside DemucsSeparator's whole-track normalisation
-    (audio_separator defaults: shifts 2, overlap 0.25, segments of the model's training length), on the device."""
+    (audio_separator defaults: shifts 2, overlap 0.25, segments of the model's training length), on the device.  ``net`` may be a list of
+    member networks with a per-source ``weights`` matrix (``[[w per source] per member]``, None: all ones): a demucs ``BagOfModels``,
+    ``est[s] = sum_m w[m][s] out_m[s] / sum_m w[m][s]`` (demucs 4 apply.py, restated -- PARITY UNPINNED)."""
 
-    def __init__(self, net: HTDemucs, shifts: int = 2, overlap: float = 0.25, seed: int = 0, sharded: bool = False, group=None,
-                 lanes: Optional[int] = None, graphs: Optional[bool] = None, contraction: str = "exact"):
+    def __init__(self, net, shifts: int = 2, overlap: float = 0.25, seed: int = 0, sharded: bool = False, group=None,
+                 lanes: Optional[int] = None, graphs: Optional[bool] = None, contraction: str = "exact", weights=None):
         """``lanes``: (shift, segment) units in flight at once, each on a HIP stream of its own (default: 4 on a GPU, 1 elsewhere).  One
         segment of htdemucs_6s is ~450 launches of mostly small kernels (grids of 42-170 workgroups on 256 CUs): units are independent,
         so running a few side by side fills the chip; the weighted sums are kept per lane and added at the end."""
-        self.net, self.ctx = net, net.ctx
+        nets = list(net) if isinstance(net, (list, tuple)) else [net]
+        if not nets:
+            raise AlsepError("DemucsRunner: no network")
+        first = nets[0].cfg
+        for n in nets[1:]:
+            if (n.cfg.sources, n.cfg.samplerate, n.cfg.audio_channels) != (first.sources, first.samplerate, first.audio_channels):
+                raise AlsepError("DemucsRunner: the members of a bag must agree on sources, samplerate and audio_channels "
+                                 f"({first.sources} / {first.samplerate} / {first.audio_channels} vs {n.cfg.sources} / {n.cfg.samplerate} / "
+                                 f"{n.cfg.audio_channels})")
+            if n.ctx is not nets[0].ctx:
+                raise AlsepError("DemucsRunner: the members of a bag must share one context")
+        from .th_reader import bag_weights
+        self.nets = nets
+        self.weights = bag_weights(weights, len(nets), first.S, "DemucsRunner")
+        self.net, self.ctx = nets[0], nets[0].ctx
         # ``contraction="split"`` (opt-in): the network's float32 convolutions / GEMMs run as split-half products on the f16 matrix pipe
         # (csrc/nn_f32s.h: float32 in and out, 2^-22 per product) for the duration of a track, on ONE lane; a track during which an operand
         # left the half range is run again on the exact f32 MFMA kernels.  Measured (10 min, one GPU): exact with four lanes 1.66 s; split
@@ -553,26 +590,28 @@ class DemucsRunner:
         if graphs is None:
             graphs = os.environ.get("ALSEP_DEMUCS_GRAPH", "0") != "0"
         self.graphs = bool(graphs) and self.ctx.device.type == "cuda"
-        self._lane_nets: List[tuple] = []                      # [(HTDemucs view, torch stream)], built on first use
-        self._graphs: Dict[int, list] = {}                     # lane index -> [(graph, static input, static output)] x graphs_per_lane
-        self._graph_turn: Dict[int, int] = {}
+        self._lane_nets: List[tuple] = []                      # [([member network views], torch stream)], built on first use
+        self._graphs: Dict[tuple, list] = {}                   # (lane, member) -> [(graph, static input, static output)] x graphs_per_lane
+        self._graph_turn: Dict[tuple, int] = {}
         self.graphs_per_lane = max(1, int(os.environ.get("ALSEP_RUNNER_GRAPHS_PER_LANE", "2")))
 
     def _lanes(self):
         if not self._lane_nets:
             first = 0 if self.graphs else 1                    # a capture needs a non-default stream: with graphs lane 0 gets its own too
             if not self.graphs:
-                self._lane_nets = [(self.net, None)]
+                self._lane_nets = [(self.nets, None)]
             for _ in range(first, self.lanes):
                 st = torch.cuda.Stream(device=self.ctx.device)
-                self._lane_nets.append((self.net.on_stream(Context(self.ctx.device, stream=st.cuda_stream)), st))
+                lctx = Context(self.ctx.device, stream=st.cuda_stream)          # one context per lane, shared by the members' views
+                self._lane_nets.append(([n.on_stream(lctx) for n in self.nets], st))
         return self._lane_nets
 
-    def _forward_unit(self, k: int, lane_net, st, chunk: torch.Tensor) -> torch.Tensor:
-        """the network on one [2, seg] segment on lane k's stream: eagerly, or -- from the lane's second unit on -- as a graph replay"""
+    def _forward_unit(self, key: tuple, lane_net, st, chunk: torch.Tensor) -> torch.Tensor:
+        """the network on one [2, seg] segment on the stream of lane key[0] (key = (lane, member)): eagerly, or -- from the lane's second
+        unit of that member on -- as a graph replay"""
         if not self.graphs:
             return lane_net.forward(chunk)
-        slots = self._graphs.setdefault(k, [])                  # two captures per lane, replayed in turn (roformer.RoformerRunner._forward_chunk)
+        slots = self._graphs.setdefault(key, [])                # two captures per lane, replayed in turn (roformer.RoformerRunner._forward_chunk)
         if len(slots) < self.graphs_per_lane:
             y = lane_net.forward(chunk)                         # eager first: plans, tables, workspaces outside a capture
             st.synchronize()
@@ -582,32 +621,48 @@ class DemucsRunner:
                 static_out = lane_net.forward(static_in)
             slots.append((g, static_in, static_out))
             return y
-        turn = self._graph_turn.get(k, 0)
-        self._graph_turn[k] = (turn + 1) % len(slots)
+        turn = self._graph_turn.get(key, 0)
+        self._graph_turn[key] = (turn + 1) % len(slots)
         g, static_in, static_out = slots[turn]
         static_in.copy_(chunk)
         g.replay()
         return static_out
 
-    def units(self, length: int):
-        """[(root offset of the view, view length, chunk offset in the view, chunk length, out offset)] over all shifts"""
-        cfg = self.net.cfg
-        seg = cfg.segment_samples
-        stride = int((1 - self.overlap) * seg)
+    def views(self, length: int):
+        """-> ([_View], max_shift): one view per (member, shift pass), member-major.  Member m, pass p takes offset
+        ``shift_offsets(M * shifts, max_shift, seed)[m * shifts + p]`` -- one seeded sequence continued over the members, as demucs' per-member
+        ``random.randint`` draws are (M = 1: the single model's sequence).  A member of a bag carries only the sources it weighs."""
+        M, cfg = len(self.nets), self.net.cfg
         max_shift = int(0.5 * cfg.samplerate) if self.shifts else 0
-        passes = shift_offsets(self.shifts, max_shift, self.seed) if self.shifts else [0]
+        offs = shift_offsets(M * self.shifts, max_shift, self.seed) if self.shifts else [0] * M
+        per = max(self.shifts, 1)
         out = []
-        for p, offset in enumerate(passes):
-            view_len = length + max_shift - offset if self.shifts else length
-            for off in range(0, view_len, stride):
-                out.append((p, offset, view_len, off, min(view_len - off, seg)))
-        return out, max_shift, len(passes)
+        for m, n in enumerate(self.nets):
+            seg = n.cfg.segment_samples
+            stride = int((1 - self.overlap) * seg)
+            rows = list(range(cfg.S)) if M == 1 else [s for s in range(cfg.S) if self.weights[m][s] != 0]
+            if not rows:
+                continue                                        # a member weighed 0 for every source contributes nothing
+            for p in range(per):
+                offset = offs[m * per + p] if self.shifts else 0
+                view_len = length + max_shift - offset if self.shifts else length
+                out.append(_View(m, offset, view_len, seg, stride, rows))
+        return out, max_shift
+
+    def units(self, length: int):
+        """[(view index, root offset of the view, view length, chunk offset in the view, chunk length)] over all views"""
+        views, max_shift = self.views(length)
+        out = []
+        for v, vw in enumerate(views):
+            for off in range(0, vw.view_len, vw.stride):
+                out.append((v, vw.offset, vw.view_len, off, min(vw.view_len - off, vw.seg)))
+        return out, max_shift, len(views)
 
     def separate(self, mix: torch.Tensor) -> Dict[str, torch.Tensor]:
         """mix [2, L] on the device -> {source name: [2, L]} (sources in the model's order)"""
         if self.contraction != "split":
             return self._separate(mix)
-        ctxs = [self.ctx] + [ln.ctx for ln, _ in self._lanes() if ln.ctx is not self.ctx]
+        ctxs = [self.ctx] + [lnets[0].ctx for lnets, _ in self._lanes() if lnets[0].ctx is not self.ctx]
         try:
             for c in ctxs:
                 c.set_nn_contraction(True)
@@ -616,7 +671,14 @@ class DemucsRunner:
         finally:
             for c in ctxs:
                 c.set_nn_contraction(False)
-        if any(exceeded):
+        exceeded = any(exceeded)
+        if self.sharded:
+            # every rank must take the same branch: a re-run on one rank alone would issue its collectives with no partner
+            import torch.distributed as tdist
+            flag = torch.tensor([1 if exceeded else 0], dtype=torch.int32, device=self.ctx.device)
+            tdist.all_reduce(flag, op=tdist.ReduceOp.MAX, group=self.group)
+            exceeded = bool(int(flag.item()))
+        if exceeded:
             import logging
             logging.getLogger(__name__).warning("DemucsRunner: an operand left the half range (|x| > 65504) during this track -- running it "
                                                 "again on the exact float32 kernels")
@@ -630,20 +692,20 @@ class DemucsRunner:
         lib, h = ctx.lib, ctx.handle
         mix = mix.contiguous().float()
         L = mix.shape[-1]
-        S, seg = cfg.S, cfg.segment_samples
-        # ref = mix.mean(0); mix = (mix - ref.mean()) / ref.std()
+        S = cfg.S
+        # ref = mix.mean(0); mix = (mix - ref.mean()) / ref.std()  -- once per track, shared by all members
         ref, right = mix[0].clone(), mix[1].clone()             # own (16-byte aligned) buffers: alsep_axpby moves float4
         ctx.check(lib.alsep_axpby(h, 0.5, _lib.ptr(right), 0.5, _lib.ptr(ref), L), "alsep_axpby")
         stats = net._meanstd(ref, L)
         norm = ctx.empty((2, L))
         stats2 = torch.cat([stats, stats])                      # the same (mean, std) for both channels; kept alive across the call
         ctx.check(lib.alsep_nn_affine_stats(h, _lib.ptr(mix), _lib.ptr(norm), _lib.ptr(stats2), 2, L, 0.0, 0), "alsep_nn_affine_stats")
-        units, max_shift, n_pass = self.units(L)
+        views, max_shift = self.views(L)
+        units, _, n_view = self.units(L)
         root = ctx.zeros((2, L + 2 * max_shift))
         root[:, max_shift:max_shift + L] = norm
         total = root.shape[-1]
-        weight = torch.cat([torch.arange(1, seg // 2 + 1), torch.arange(seg - seg // 2, 0, -1)]).float()
-        weight = (weight / weight.max()).to(ctx.device)
+        tri = {vw.seg: _tri(vw.seg).to(ctx.device) for vw in views}
         rank, world = 0, 1
         if self.sharded:
             import torch.distributed as tdist
@@ -651,35 +713,40 @@ class DemucsRunner:
         from . import dist as adist
         lo, hi = adist.window_range(len(units), world, rank)
         lanes = self._lanes()[: max(1, min(self.lanes, hi - lo))]
-        # one weighted sum per (lane, shift pass), view coordinates; lane 0 runs on this context's stream, the others on their own
-        accs = [[ctx.zeros((S * 2, L + max_shift)) for _ in range(n_pass)] for _ in lanes]
+        width = L + max_shift
+        # one weighted sum per (lane, view) over the view's carried sources, view coordinates; lane 0 runs on this context's stream
+        accs = [[ctx.zeros((len(vw.rows) * 2, width)) for vw in views] for _ in lanes]
         main = torch.cuda.current_stream(ctx.device) if (len(lanes) > 1 or self.graphs) else None
         for _, st in lanes:
             if st is not None:
-                st.wait_stream(main)                             # root, weight and the zeroed sums are ready
+                st.wait_stream(main)                             # root, weights and the zeroed sums are ready
 
-        def run_unit(k, lane_net, st, lane_acc, unit):
-            p, offset, view_len, off, cl = unit
+        def run_unit(k, lane_nets, st, lane_acc, unit):
+            v, offset, view_len, off, cl = unit
+            vw = views[v]
+            lane_net = lane_nets[vw.m]
             lctx = lane_net.ctx
+            seg = vw.seg
             delta = seg - cl
             start = offset + off - delta // 2
             end = start + seg
             cs, ce = max(0, start), min(total, end)
             chunk = lctx.zeros((2, seg))
             chunk[:, cs - start: cs - start + (ce - cs)] = root[:, cs:ce]
-            y = self._forward_unit(k, lane_net, st, chunk)                           # [S, 2, seg]
-            src = C.c_void_p(y.data_ptr() + 4 * (delta // 2))
-            dst = C.c_void_p(lane_acc[p].data_ptr() + 4 * off)
-            lctx.check(lctx.lib.alsep_nn_vec_fma(lctx.handle, dst, src, _lib.ptr(weight), S * 2, cl, L + max_shift, seg), "alsep_nn_vec_fma")
+            y = self._forward_unit((k, vw.m), lane_net, st, chunk)                  # [S, 2, seg]
+            for s0, n, j0 in vw.runs:
+                src = C.c_void_p(y.data_ptr() + 4 * (s0 * 2 * seg + delta // 2))
+                dst = C.c_void_p(lane_acc[v].data_ptr() + 4 * (j0 * 2 * width + off))
+                lctx.check(lctx.lib.alsep_nn_vec_fma(lctx.handle, dst, src, _lib.ptr(tri[seg]), n * 2, cl, width, seg), "alsep_nn_vec_fma")
 
         for i, unit in enumerate(units[lo:hi]):
             k = i % len(lanes)
-            lane_net, st = lanes[k]
+            lane_nets, st = lanes[k]
             if st is None:
-                run_unit(k, lane_net, st, accs[0], unit)
+                run_unit(k, lane_nets, st, accs[0], unit)
             else:
                 with torch.cuda.stream(st):                      # torch's allocator ties the lane's temporaries to its stream
-                    run_unit(k, lane_net, st, accs[k], unit)
+                    run_unit(k, lane_nets, st, accs[k], unit)
         acc = accs[0]
         for k, (_, st) in enumerate(lanes):
             if st is None:
@@ -687,30 +754,30 @@ class DemucsRunner:
             main.wait_stream(st)
             if k == 0:
                 continue
-            for p in range(n_pass):
+            for p in range(n_view):
                 ctx.check(lib.alsep_axpby(h, 1.0, _lib.ptr(accs[k][p]), 1.0, _lib.ptr(acc[p]), acc[p].numel()), "alsep_axpby")
-        # per pass: divide by the summed weights of that pass, cut the view back to the track, average the passes
-        stride = int((1 - self.overlap) * seg)
-        passes = shift_offsets(self.shifts, max_shift, self.seed) if self.shifts else [0]
-        width = L + max_shift
+        # per view: the summed triangular weights of its units
         sws = []
-        for p, offset in enumerate(passes):
-            view_len = L + max_shift - offset if self.shifts else L
+        for vw in views:
             sw = torch.zeros(width)
-            for off in range(0, view_len, stride):
-                cl = min(view_len - off, seg)
-                sw[off:off + cl] += _tri(seg)[:cl]
+            for off in range(0, vw.view_len, vw.stride):
+                cl = min(vw.view_len - off, vw.seg)
+                sw[off:off + cl] += _tri(vw.seg)[:cl]
             sws.append(sw.to(ctx.device))
+        bag = len(self.nets) > 1
         if self.sharded and world > 1:
-            # a rank's units are a contiguous run, so in every pass it owns the span from its first unit's offset to the next
+            # a rank's units are a contiguous run, so in every view it owns the span from its first unit's offset to the next
             # rank's (the last one: to the end).  Its units reach at most seg - stride samples beyond that span: those seam sums travel in
-            # one small all-gather and are added by the span's owner; every rank divides ITS spans by the summed weights, and ONE
-            # all-gather of the finished spans (both passes side by side) gives every rank the whole passes -- no full-length all-reduce.
-            seam = max(seg - stride, 1)
+            # one small all-gather and are added by the span's owner; every rank divides ITS spans by the summed weights (a bag: the
+            # finishing kernel divides), and ONE all-gather of the finished spans (all views side by side; views that carry fewer sources
+            # padded to the most rows) gives every rank the whole views -- no full-length all-reduce.
+            rows2 = max(len(vw.rows) for vw in views) * 2
+            seam_w = max(max(vw.seg - vw.stride, 1) for vw in views)
             bounds = [adist.window_range(len(units), world, q) for q in range(world)]
             ranges, tails = [], []
-            for p in range(n_pass):
-                firsts = []                                                     # first offset of rank q's units in pass p (None: none there)
+            for p, vw in enumerate(views):
+                seam = max(vw.seg - vw.stride, 1)
+                firsts = []                                                     # first offset of rank q's units in view p (None: none there)
                 for q_lo, q_hi in bounds:
                     offs = [u[3] for u in units[q_lo:q_hi] if u[0] == p]
                     firsts.append(offs[0] if offs else None)
@@ -718,21 +785,23 @@ class DemucsRunner:
                 rg = [None] * world
                 for i, q in enumerate(owners):
                     rg[q] = (0 if i == 0 else firsts[q], firsts[owners[i + 1]] if i + 1 < len(owners) else width)
-                for q in range(world):                                          # a rank without units in this pass: an empty span, placed
+                for q in range(world):                                          # a rank without units in this view: an empty span, placed
                     if rg[q] is None:                                           # so that the spans stay ascending and cover [0, width)
                         at = next((rg[r][0] for r in range(q + 1, world) if rg[r] is not None and firsts[r] is not None), width)
                         rg[q] = (at, at)
                 ranges.append(rg)
                 own_lo, own_hi = rg[rank]
-                tail = ctx.zeros((S * 2, seam))
+                tail = ctx.zeros((rows2, seam_w))
                 n_tail = max(0, min(seam, width - own_hi)) if own_hi > own_lo else 0
                 if n_tail:
-                    tail[:, :n_tail] = acc[p][:, own_hi: own_hi + n_tail]
+                    tail[:acc[p].shape[0], :n_tail] = acc[p][:, own_hi: own_hi + n_tail]
                 tails.append(tail)
-            got = adist.all_gather_fixed(torch.stack(tails), self.group)        # [world, n_pass, 2 S, seam]
+            got = adist.all_gather_fixed(torch.stack(tails), self.group)        # [world, n_view, rows2, seam_w]
             pieces = []
-            for p in range(n_pass):
+            for p, vw in enumerate(views):
+                seam = max(vw.seg - vw.stride, 1)
                 own_lo, own_hi = ranges[p][rank]
+                r2 = acc[p].shape[0]
                 own = acc[p][:, own_lo:own_hi].contiguous()
                 for q in range(rank):                                           # earlier owners whose units reach into this span
                     q_lo, q_hi = ranges[p][q]
@@ -740,12 +809,18 @@ class DemucsRunner:
                         continue
                     lo_, hi_ = max(q_hi, own_lo), min(q_hi + seam, own_hi)
                     if hi_ > lo_:
-                        own[:, lo_ - own_lo: hi_ - own_lo] += got[q, p][:, lo_ - q_hi: hi_ - q_hi]
-                if own_hi > own_lo:
+                        own[:, lo_ - own_lo: hi_ - own_lo] += got[q, p][:r2, lo_ - q_hi: hi_ - q_hi]
+                if own_hi > own_lo and not bag:
                     swp = sws[p][own_lo:own_hi].contiguous()
                     ctx.check(lib.alsep_nn_vec_div(h, _lib.ptr(own), _lib.ptr(swp), S * 2, own_hi - own_lo), "alsep_nn_vec_div")
+                if r2 < rows2:
+                    own = torch.cat([own, ctx.zeros((rows2 - r2, own_hi - own_lo))])
                 pieces.append(own)
-            acc = adist.all_gather_multi_ranges(pieces, ranges, [width] * n_pass, self.group)
+            acc = adist.all_gather_multi_ranges(pieces, ranges, [width] * n_view, self.group)
+        if bag:
+            return self._finish_bag(views, acc, sws, stats, max_shift, L)
+        passes = [vw.offset for vw in views]
+        n_pass = n_view
         out = ctx.zeros((S * 2, L))
         for p, offset in enumerate(passes):
             view_len = L + max_shift - offset if self.shifts else L
@@ -760,6 +835,37 @@ class DemucsRunner:
         ctx.check(lib.alsep_nn_affine_stats(h, _lib.ptr(out), _lib.ptr(res), _lib.ptr(stats), 1, S * 2 * L, 0.0, 1), "alsep_nn_affine_stats")
         res = res.view(S, 2, L)
         return {name: res[i] for i, name in enumerate(cfg.sources)}
+
+    def _finish_bag(self, views, acc, sws, stats, max_shift: int, L: int) -> Dict[str, torch.Tensor]:
+        """all views -> the stems in ONE launch (alsep_demucs_bag_finish): divide by the summed weights, cut the view back to the track,
+        weigh per source (w[m][s] / sum_m w[m][s] / passes), add, de-normalise"""
+        ctx, cfg = self.ctx, self.net.cfg
+        S = cfg.S
+        totals = [sum(self.weights[m][s] for m in range(len(self.nets))) for s in range(S)]
+        per = max(self.shifts, 1)
+        row, coef, cuts, lds = [], [], [], []
+        for vw, a, sw in zip(views, acc, sws):
+            cut = max_shift - vw.offset
+            if not (a.is_contiguous() and a.dim() == 2 and a.shape[0] >= len(vw.rows) * 2 and 0 <= cut and cut + L <= a.shape[1]
+                    and sw.numel() >= cut + L):
+                raise AlsepError("DemucsRunner: a view's sums do not cover the track")       # the kernel trusts these extents
+            j = {s: i for i, s in enumerate(vw.rows)}
+            row += [j.get(s, -1) for s in range(S)]
+            coef += [self.weights[vw.m][s] / totals[s] / per for s in range(S)]
+            cuts.append(cut)
+            lds.append(a.shape[1])
+        dev = ctx.device
+        acc_p = torch.tensor([a.data_ptr() for a in acc], dtype=torch.int64).to(dev)
+        ws_p = torch.tensor([w.data_ptr() for w in sws], dtype=torch.int64).to(dev)
+        ld_t = torch.tensor(lds, dtype=torch.int64).to(dev)
+        cut_t = torch.tensor(cuts, dtype=torch.int32).to(dev)
+        row_t = torch.tensor(row, dtype=torch.int32).to(dev)
+        coef_t = torch.tensor(coef, dtype=torch.float64).float().to(dev)
+        out = ctx.empty((S, 2, L))
+        ctx.check(ctx.lib.alsep_demucs_bag_finish(ctx.handle, _lib.ptr(acc_p), _lib.ptr(ws_p), _lib.ptr(ld_t), _lib.ptr(cut_t), _lib.ptr(row_t),
+                                                  _lib.ptr(coef_t), _lib.ptr(stats), _lib.ptr(out), len(views), S, L),
+                  "alsep_demucs_bag_finish")
+        return {name: out[i] for i, name in enumerate(cfg.sources)}
 
 
 _TRI: Dict[int, torch.Tensor] = {}

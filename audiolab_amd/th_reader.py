@@ -195,3 +195,58 @@ def resolve_demucs_yaml(model_file_dir: str, yaml_name: str):
     if not hits:
         raise AlsepError(f"{ypath} names model '{sig}', but no {sig}*.th is in {model_file_dir}")
     return os.path.join(model_file_dir, hits[0])
+
+
+def bag_weights(weights, n_models: int, n_sources: int, where: str):
+    """demucs' ``BagOfModels(models, weights)`` rule for the per-source weight matrix: ``weights[m][s]`` for every member m and source s
+    (None: all ones, demucs' default).  Refused here rather than left to demucs: a shape other than n_models x n_sources, a negative or
+    non-finite weight, and a source whose weights sum to 0 (demucs would divide by zero).  -> [[float] * n_sources] * n_models"""
+    import math
+    if weights is None:
+        return [[1.0] * n_sources for _ in range(n_models)]
+    if n_sources < 1 or not isinstance(weights, (list, tuple)) or len(weights) != n_models or \
+            not all(isinstance(r, (list, tuple)) and len(r) == n_sources for r in weights):
+        raise AlsepError(f"{where}: 'weights' must be {n_models} rows (one per model) of {n_sources} weights (one per source)")
+    try:
+        w = [[float(v) for v in r] for r in weights]
+    except (TypeError, ValueError) as e:
+        raise AlsepError(f"{where}: 'weights' holds a value that is not a number") from e
+    if not all(math.isfinite(v) and v >= 0 for r in w for v in r):
+        raise AlsepError(f"{where}: a weight is negative or not finite")
+    for s in range(n_sources):
+        if sum(r[s] for r in w) == 0:
+            raise AlsepError(f"{where}: the weights of source {s} sum to 0 (demucs would divide by zero)")
+    return w
+
+
+def resolve_demucs_bag(model_file_dir: str, yaml_name: str, n_sources=None):
+    """``<dir>/<name>.yaml`` of demucs' remote model zoo (demucs.repo / states, restated -- PARITY UNPINNED: ``models: [signature, ...]``,
+    optional ``weights: [[w per source] per model]`` and ``segment``) -> (the .th path of every member, in the yaml's order; the weight
+    matrix; the bag's segment or None); None when the yaml is absent.  A member whose ``<signature>*.th`` is missing is an error: a bag is
+    read whole or not at all.  ``n_sources`` (when the caller knows it) fixes the matrix' width; without it a yaml without ``weights``
+    gives None (= all ones, bag_weights) and one with weights is checked for a consistent width.  The bag's ``segment`` does not lengthen
+    an HTDemucs member (it keeps its training length): it is returned for information only."""
+    ypath = os.path.join(model_file_dir, yaml_name)
+    if not os.path.isfile(ypath):
+        return None
+    import yaml
+    y = yaml.safe_load(open(ypath)) or {}
+    if not isinstance(y, dict):
+        raise AlsepError(f"{ypath}: not a demucs bag description (expected a mapping with 'models')")
+    sigs = [str(s) for s in (y.get("models") or [])]
+    if not sigs:
+        raise AlsepError(f"{ypath}: names no models")
+    paths = []
+    for sig in sigs:
+        hits = sorted(f for f in os.listdir(model_file_dir) if f.startswith(sig) and f.endswith(".th"))
+        if not hits:
+            raise AlsepError(f"{ypath} names model '{sig}', but no {sig}*.th is in {model_file_dir}")
+        paths.append(os.path.join(model_file_dir, hits[0]))
+    weights = y.get("weights")
+    if weights is not None or n_sources is not None:
+        width = n_sources
+        if width is None:
+            width = len(weights[0]) if isinstance(weights, (list, tuple)) and weights and isinstance(weights[0], (list, tuple)) else -1
+        weights = bag_weights(weights, len(sigs), width, ypath)
+    segment = y.get("segment")
+    return paths, weights, (float(segment) if segment is not None else None)

@@ -320,6 +320,13 @@ int alsep_demucs_spec_out(alsep_ctx* ctx, const float* x, const float* stats, fl
                           int t_off, float scale);
 /* out [B,S,2,L] = (xt [B,L,S*2] * stdt + meant) + xs [B*S,2,L]   (the last lines of HTDemucs.forward) */
 int alsep_demucs_mix_out(alsep_ctx* ctx, const float* xt, const float* statst, const float* xs, float* out, int64_t B, int S, int64_t L);
+/* a bag of Demucs models, last step: V views (one shift pass of one member each) -> the stems out [S,2,L] in one pass,
+ *   out[s,c,t] = stats[0] + stats[1] * sum_v coef[v*S+s] * q_v(row[v*S+s]*2 + c, t + cut[v]),
+ *   q_v(r, x) = wsum[v][x] != 0 ? acc[v][r * ld[v] + x] / wsum[v][x] : 0;  row[v*S+s] < 0: view v does not carry source s.
+ * Every array is device memory: acc / wsum hold V device pointers, ld (int64) and cut (int32) V entries, row (int32) and coef V*S.
+ * The caller guarantees 0 <= cut[v], cut[v] + L <= ld[v] and that wsum[v] holds cut[v] + L values.  1 <= S <= 8, 1 <= V <= 64. */
+int alsep_demucs_bag_finish(alsep_ctx* ctx, const float* const* acc, const float* const* wsum, const int64_t* ld, const int32_t* cut,
+                            const int32_t* row, const float* coef, const float* stats, float* out, int V, int S, int64_t L);
 
 /* ---- Roformer family (BS-RoFormer / Mel-Band RoFormer: the first members of the reference's default ensemble and its de-reverb /
  * de-echo models, stem_separator.py:379-382, 796-797; network source in the un-vendored audio-separator -- PARITY UNPINNED).  Further
