@@ -3254,16 +3254,19 @@ int run_pix_stream(alsep_ctx* ctx, int mode, const GemmLayer& L, const bf16_t* X
         const int64_t gx = std::min<int64_t>(ceil_div64(ntile, 4), 256);
         hipLaunchKernelGGL(ds48_stream_kernel, dim3((unsigned)gx), dim3(kThreads), lds, ctx->stream, X, Y, (const bf16_t*)L.wfrag.p,
                            (const float*)L.scale.p, (const float*)L.shift.p, ncols, Tp, Fp);
+        note_launch(ctx, "ds48_stream_kernel");
     } else if (mode == PIX_DS && L.M == DsSplitCfg<96>::M) { // 96 -> 144
         const size_t lds = 64 * DsSplitCfg<96>::MS * sizeof(bf16_t);
         const int64_t gx = std::min<int64_t>(ntile, 512);
         hipLaunchKernelGGL((ds_split_stream_kernel<96, 2>), dim3((unsigned)gx), dim3(kThreads), lds, ctx->stream, X, Y,
                            (const bf16_t*)L.wfrag.p, (const float*)L.scale.p, (const float*)L.shift.p, ncols, Tp, Fp);
+        note_launch(ctx, "ds_split_stream_kernel<96>");
     } else if (mode == PIX_DS) {                             // 144 -> 192
         const size_t lds = 64 * DsSplitCfg<144>::MS * sizeof(bf16_t);
         const int64_t gx = std::min<int64_t>(ntile, 512);
         hipLaunchKernelGGL((ds_split_stream_kernel<144, 1>), dim3((unsigned)gx), dim3(kThreads), lds, ctx->stream, X, Y,
                            (const bf16_t*)L.wfrag.p, (const float*)L.scale.p, (const float*)L.shift.p, ncols, Tp, Fp);
+        note_launch(ctx, "ds_split_stream_kernel<144>");
     } else {
 #define ALSEP_US(CIN_, C2_, NI_, OCC_, GX_)                                                                                 \
     {                                                                                                                       \
@@ -3274,6 +3277,7 @@ int run_pix_stream(alsep_ctx* ctx, int mode, const GemmLayer& L, const bf16_t* X
         hipLaunchKernelGGL((us_stream_kernel<CIN_, C2_, NI_, OCC_>), dim3((unsigned)gx), dim3(kThreads), U::lds_bytes,      \
                            ctx->stream, X, Y, (const bf16_t*)L.wfrag.p, (const float*)L.scale.p, (const float*)L.shift.p,   \
                            skip, ncols, Tp, Fp);                                                                            \
+        note_launch(ctx, "us_stream_kernel<" #CIN_ "," #C2_ ">");                                                          \
     }
         if (L.K == 96) ALSEP_US(96, 48, 4, 1, 512)               // 96 -> 48
         else if (L.K == 144) ALSEP_US(144, 96, 2, 2, 512)        // 144 -> 96: 32-pixel tiles, two workgroups per CU

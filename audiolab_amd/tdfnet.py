@@ -103,7 +103,11 @@ def folded_tensors(sd: Dict[str, torch.Tensor], cfg: TDFNetConfig) -> Dict[str, 
                 lin, bn = f"{src}.tdf.{3 * j}", f"{src}.tdf.{3 * j + 1}"
                 out[f"{dst}.tdf.{j}.weight"] = sd[lin + ".weight"]
                 # the Linear bias is per output FEATURE (f'), BN is per CHANNEL: keep them apart
-                s, sh = fold_batchnorm(sd, lin, bn, conv_bias_per_channel=False)
+                if bn + ".weight" in sd:
+                    s, sh = fold_batchnorm(sd, lin, bn, conv_bias_per_channel=False)
+                else:                                 # no BatchNorm after this linear: identity per CHANNEL (not per feature)
+                    c = sd[f"{src}.tfc.H.0.0.weight"].shape[0]
+                    s, sh = torch.ones(c), torch.zeros(c)
                 out[f"{dst}.tdf.{j}.scale"], out[f"{dst}.tdf.{j}.shift"] = s, sh
                 if lin + ".bias" in sd:
                     out[f"{dst}.tdf.{j}.bias"] = sd[lin + ".bias"]
