@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libalsep.so")
 F32, BF16, F16 = 0, 1, 2
 PROF_CONV3X3, PROF_CONV3X3_SMALL, PROF_TDF, PROF_PIX, PROF_POINTWISE, PROF_STFT, PROF_ISTFT = 1, 2, 3, 4, 5, 6, 7
 PROF_CONV3X3_REGW, PROF_CONV3X3_PIPE, PROF_CONV3X3_BIG, PROF_CONV3X3_BIG3 = 8, 9, 10, 11
-PROF_NN_GEMM, PROF_NN_CONV, PROF_NN_GEMM_H, PROF_NN_ATTN_H, PROF_NN_CONV_H = 12, 13, 14, 15, 16
+PROF_NN_GEMM, PROF_NN_CONV, PROF_NN_GEMM_H, PROF_NN_ATTN_H, PROF_NN_CONV_H, PROF_NN_DCONV_H, PROF_NN_NORM_H = 12, 13, 14, 15, 16, 17, 18
 LAYOUT_REF, LAYOUT_NHWC = 0, 1
 ABI_VERSION = 1
 
@@ -159,6 +159,12 @@ _SIGNATURES = {
     "alsep_nn_attention_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                          C.c_int64, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
     "alsep_nn_rotary_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "alsep_nn_conv_h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64] +
+                        [C.c_int] * 16),
+    "alsep_nn_norm_h_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "alsep_nn_norm_h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float,
+                                  C.c_int, C.c_void_p]),
+    "alsep_nn_xattention_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_int64] * 6 + [C.c_float]),
     "alsep_roformer_bandsplit_in": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "alsep_reverb_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "alsep_reverb_xcorr_argmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int64,

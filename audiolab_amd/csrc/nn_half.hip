@@ -15,6 +15,7 @@
 //   nn_attn_h_kernel     softmax(Q K^T) V of a packed f16 q | k | v projection in one pass (no score matrix in HBM), rotary embedding on
 //                        load, head gates in the epilogue, f16 out
 //   roformer_bandsplit_in_kernel   gather + RMSNorm of every band of a frame -> zero-padded f16 rows of one batched Linear
+//   nn_demucs_h.h        HTDemucs' half-precision mode: Demucs-geometry convolution, GroupNorm / LayerNorm to half, cross-attention
 #include "alsep_common.h"
 #include <alsep_gfx950_asm.h>
 #include "nn_gemm_h2.h"
@@ -543,7 +544,8 @@ __device__ __forceinline__ void h8_to_f(const h16x8& v, f32x4& a, f32x4& b) {
 // structure minimises those: the K / V staging and K's rotation are shared by twice the queries, a chunk is 64 keys (half the barriers
 // and accumulator rescales per key), the scores are kept in the log2 domain (scale log2(e) folded into Q: one v_exp_f32 per score,
 // no multiply), keys beyond the sequence are masked only in the one chunk that has them, and V^T is scattered into LDS as 4-byte
-// pairs of keys.
+// pairs of keys.  nn_demucs_h.h holds a copy for cross-attention (nn_xattn_h_kernel: separate q and k | v, Lq != Lk): a fix here
+// belongs there too.
 template <int QB>
 __global__ void __launch_bounds__(kHThreads)
 nn_attn_h_kernel(const _Float16* __restrict__ qkv, _Float16* __restrict__ out, int L, int heads, int64_t seq_stride, int64_t row_stride,
@@ -1003,3 +1005,6 @@ extern "C" int alsep_nn_attention_f16(alsep_ctx* ctx, const void* qkv, void* out
     return ALSEP_OK;
 }
 #endif  // !ALSEP_NN_HALF_CONV_TU
+#ifndef ALSEP_NN_HALF_CONV_TU
+#include "nn_demucs_h.h"
+#endif

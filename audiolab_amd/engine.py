@@ -187,7 +187,8 @@ class Separator:
                  dtype: Optional[torch.dtype] = None, sample_rate: int = 44100, chunks: int = 0, margin: int = 44100,
                  denoise: bool = False, max_batch: int = 32, sharded: bool = False, roster: Optional[Dict[str, tuple]] = None,
                  chunker: str = "margin", overlap: float = 0.25, compensate: Optional[float] = None,
-                 allow_synthetic: bool = False, normalization_threshold: float = 0.9, f32_contraction: str = "split", nn_contraction: str = "exact", **_ignored):
+                 allow_synthetic: bool = False, normalization_threshold: float = 0.9, f32_contraction: str = "split", nn_contraction: str = "exact",
+                 demucs_precision: str = "f32", **_ignored):
         """``allow_synthetic=True`` (bench, tests): a roster name without a weight file gets seeded random-init weights.
         The default refuses to: a missing model file is an error, never plausible-looking noise."""
         self.log_level = log_level
@@ -222,6 +223,11 @@ class Separator:
         if nn_contraction not in ("split", "exact"):
             raise AlsepError("nn_contraction must be 'split' or 'exact'")
         self.nn_contraction = nn_contraction
+        # HTDemucs' half-precision mode (htdemucs.HTDemucs(precision="f16")) is opt-in: the default keeps float32 for every caller, whatever
+        # use_autocast says (making it the use_autocast default waits for real weights)
+        if demucs_precision not in ("f32", "f16"):
+            raise AlsepError("demucs_precision must be 'f32' or 'f16'")
+        self.demucs_precision = demucs_precision
         self.model_instance: Optional[_ModelInstance] = None
         self._cache: Dict[str, _ModelInstance] = {}
 
@@ -329,7 +335,8 @@ class Separator:
         ``kwargs``, ``state`` as the weights); ``<dir>/<name>.pt`` (a plain state_dict with demucs' parameter names; single models only);
         with allow_synthetic, seeded random-init ones (a bag entry: ``members`` networks seeded from ``<name>#<i>``, the entry's ``weights``).
         A yaml of several models gives a bag (one network per member, all read -- a member file missing is an error, never a synthetic
-        stand-in); the members must agree on sources, samplerate and channels.  float32 (the kernels of this family are fp32)."""
+        stand-in); the members must agree on sources, samplerate and channels.  float32, or with ``Separator(demucs_precision="f16")`` the
+        half-precision mode for every member (float32 with a WARNING where the head size is not 64)."""
         from . import th_reader
         cfg = entry[1]
         opts = entry[2] if len(entry) > 2 else {}
@@ -381,15 +388,22 @@ class Separator:
                            self.model_file_dir)
         elif sd is not None:
             weights = "real"
+        precision = self.demucs_precision
+        if precision == "f16":
+            bad = [c for c, _ in (members or [(cfg, sd)]) if c.bottom_channels % c.t_heads or c.bottom_channels // c.t_heads != 64]
+            if bad:
+                logger.warning("%s: head size %d / %d is not 64 -- the half-precision Demucs mode needs 64; running in float32", model_filename,
+                               bad[0].bottom_channels, bad[0].t_heads)
+                precision = "f32"
         if members is not None:
-            nets = [HTDemucs(c, sd_i, ctx=self.ctx) for c, sd_i in members]
+            nets = [HTDemucs(c, sd_i, ctx=self.ctx, precision=precision) for c, sd_i in members]
             net, cfg = nets[0], nets[0].cfg
         else:
-            net = HTDemucs(cfg, sd, ctx=self.ctx)
+            net = HTDemucs(cfg, sd, ctx=self.ctx, precision=precision)
             nets = net
         inst = _ModelInstance(model_filename, net, None, cfg.sources[0].capitalize(), None)
         inst.demucs = DemucsRunner(nets, shifts=int(opts.get("shifts", 2)), overlap=float(opts.get("overlap", 0.25)), sharded=self.sharded,
-                                   contraction=self.nn_contraction, weights=bag_weights)
+                                   contraction=self.nn_contraction if precision == "f32" else "exact", weights=bag_weights)
         inst.output_dir = self.output_dir
         inst.weights = weights
         self._cache[model_filename] = inst

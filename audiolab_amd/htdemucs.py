@@ -153,23 +153,42 @@ def expected_shapes(cfg: HTDemucsConfig) -> Dict[str, Tuple[Tuple[int, ...], str
 
 
 class _Conv:
-    """weights of one convolution / linear in the layout alsep_nn_conv2d reads: [KH][KW][Cin][Cout], scale 1, shift = bias"""
+    """weights of one convolution / linear in the layout alsep_nn_conv2d reads: [KH][KW][Cin][Cout], scale 1, shift = bias.  In the
+    half-precision mode also ``wh`` [Cout][Kp] IEEE half, k = (dy, dx, ci) zero-padded to Kp (a multiple of 32): the layout of
+    alsep_nn_conv_h, and for a 1x1 with Cin % 32 == 0 the [N][K] weight of alsep_nn_gemm_f16"""
 
-    def __init__(self, ctx: Context, w4: torch.Tensor, bias: Optional[torch.Tensor]):
+    def __init__(self, ctx: Context, w4: torch.Tensor, bias: Optional[torch.Tensor], half: bool = False):
         self.kh, self.kw, self.cin, self.cout = (int(v) for v in w4.shape)
         self.w = w4.detach().float().contiguous().to(ctx.device)
         self.scale = torch.ones(self.cout, device=ctx.device)
         self.shift = (bias.detach().float() if bias is not None else torch.zeros(self.cout)).contiguous().to(ctx.device)
+        self.wh = None
+        if half:
+            k = self.kh * self.kw * self.cin
+            self.kp = -(-k // 32) * 32
+            wh = torch.zeros(self.cout, self.kp, dtype=torch.float16)
+            wh[:, :k] = w4.detach().float().permute(3, 0, 1, 2).reshape(self.cout, k).half()
+            self.wh = wh.to(ctx.device)
 
 
 class HTDemucs:
-    def __init__(self, cfg: HTDemucsConfig, state_dict: Dict[str, torch.Tensor], ctx: Optional[Context] = None):
+    def __init__(self, cfg: HTDemucsConfig, state_dict: Dict[str, torch.Tensor], ctx: Optional[Context] = None, precision: str = "f32"):
+        """``precision="f16"``: the half-precision mode (torch autocast restated): every convolution, Linear and
+        attention product reads IEEE-half operands on the f16 matrix pipe and accumulates in float32; norms, statistics, the residual
+        streams, the STFT / iSTFT and the output stages stay float32.  The float32 weights are kept as well (``forward_f32``: the
+        runner's re-run of a track whose half-precision stems are not finite)."""
         self.cfg = cfg
         self.ctx = ctx if ctx is not None else _lib.default_context(None)
+        if precision not in ("f32", "f16"):
+            raise AlsepError("HTDemucs: precision must be 'f32' or 'f16'")
         if cfg.kernel_size != 2 * cfg.stride or cfg.audio_channels != 2:
             raise AlsepError("HTDemucs: kernel_size must be 2 * stride and the input stereo")
         if cfg.bottom_channels % cfg.t_heads:
             raise AlsepError("HTDemucs: bottom_channels must be divisible by the head count")
+        if precision == "f16" and cfg.bottom_channels // cfg.t_heads != 64:
+            raise AlsepError(f"HTDemucs: the half-precision mode needs bottom_channels / t_heads == 64 (the f16 attention's head size), "
+                             f"not {cfg.bottom_channels} / {cfg.t_heads}")
+        self.precision = precision
         sd = state_dict
         dev = self.ctx.device
         from .roformer import check_shapes
@@ -183,7 +202,8 @@ class HTDemucs:
         self._plans: Dict[int, object] = {}
         self._pos: Dict[tuple, torch.Tensor] = {}
         self._ws: Optional[torch.Tensor] = None
-        self.dtype = torch.float32
+        self._ws_h: Optional[torch.Tensor] = None
+        self.dtype = torch.float16 if precision == "f16" else torch.float32
         _ = dev
 
     def on_stream(self, ctx: Context) -> "HTDemucs":
@@ -195,6 +215,17 @@ class HTDemucs:
         v = copy.copy(self)
         v.ctx = ctx
         v._plans, v._pos, v._ws = {}, {}, None
+        v._ws_h = None
+        return v
+
+    def as_f32(self) -> "HTDemucs":
+        """this network in float32 (the weights are shared; a view of an f16 network, whose float32 weights are kept)"""
+        if self.precision == "f32":
+            return self
+        import copy
+        v = copy.copy(self)
+        v.precision = "f32"
+        v._plans, v._pos, v._ws, v._ws_h = {}, {}, None, None
         return v
 
     # -- parameters ---------------------------------------------------------------------------------------
@@ -204,24 +235,25 @@ class HTDemucs:
     def _build(self, sd) -> None:
         cfg, ctx = self.cfg, self.ctx
         K = cfg.kernel_size
+        hf = self.precision == "f16"
 
         def conv_freq(p):       # Conv2d [Cout, Cin, KH, KW] -> [KH][KW][Cin][Cout]
-            return _Conv(ctx, sd[p + ".weight"].permute(2, 3, 1, 0), sd.get(p + ".bias"))
+            return _Conv(ctx, sd[p + ".weight"].permute(2, 3, 1, 0), sd.get(p + ".bias"), hf)
 
         def conv_time(p):       # Conv1d [Cout, Cin, K]: the kernel runs along H (= samples), W = 1
-            return _Conv(ctx, sd[p + ".weight"].permute(2, 1, 0)[:, None], sd.get(p + ".bias"))
+            return _Conv(ctx, sd[p + ".weight"].permute(2, 1, 0)[:, None], sd.get(p + ".bias"), hf)
 
         def conv_along_w(p):    # Conv1d applied along T of [Fr, T, C] (the DConv of the frequency branch): kernel along W
-            return _Conv(ctx, sd[p + ".weight"].permute(2, 1, 0)[None], sd.get(p + ".bias"))
+            return _Conv(ctx, sd[p + ".weight"].permute(2, 1, 0)[None], sd.get(p + ".bias"), hf)
 
         def linear(wt, bs):     # [out, in] -> 1x1
-            return _Conv(ctx, wt.t()[None, None], bs)
+            return _Conv(ctx, wt.t()[None, None], bs, hf)
 
         def tconv(p):           # ConvTranspose [Cin, Cout, K(,1)] -> 1x1 conv to K * Cout columns (k-major), bias kept for the fold
             w = sd[p + ".weight"]
             w = w[..., 0] if w.dim() == 4 else w
             cin, cout, k = w.shape
-            return _Conv(ctx, w.permute(0, 2, 1).reshape(cin, k * cout)[None, None], None), self._vec(sd[p + ".bias"]), cout
+            return _Conv(ctx, w.permute(0, 2, 1).reshape(cin, k * cout)[None, None], None, hf), self._vec(sd[p + ".bias"]), cout
 
         def dconv(p, freq):
             layers = []
@@ -431,7 +463,14 @@ class HTDemucs:
 
     # -- forward --------------------------------------------------------------------------------------------
     def forward(self, mix: torch.Tensor) -> torch.Tensor:
-        """HTDemucs.forward (eval): mix [2, L] float32 on the device, L <= segment_samples -> [S, 2, L]"""
+        """HTDemucs.forward (eval): mix [2, L] float32 on the device, L <= segment_samples -> [S, 2, L].  In the half-precision mode
+        also a batch [B, 2, L] -> [B, S, 2, L]; every sample comes out bit-identical to that sample run alone."""
+        if self.precision == "f16":
+            return self._forward_h(mix)
+        return self.forward_f32(mix)
+
+    def forward_f32(self, mix: torch.Tensor) -> torch.Tensor:
+        """the float32 network (the default mode; in the half-precision mode the re-run of a track whose stems are not finite)"""
         ctx, cfg = self.ctx, self.cfg
         lib, h = ctx.lib, ctx.handle
         if mix.dim() != 2 or mix.shape[0] != 2 or mix.dtype != torch.float32:
@@ -520,7 +559,205 @@ class HTDemucs:
         ctx.check(lib.alsep_demucs_mix_out(h, _lib.ptr(xt), _lib.ptr(stats_t), _lib.ptr(xs), _lib.ptr(out), 1, S, L), "alsep_demucs_mix_out")
         return out[..., :length_pre_pad] if length_pre_pad else out
 
+    # -- half-precision mode (precision="f16") ---------------------------------------------------------------
+    # Rounding points: a product reads IEEE half -- activations float32 in HBM are rounded as the convolution stages
+    # them, the norms that feed a Linear / convolution store half, the q | k | v projections and the attention output are half; every
+    # product accumulates in float32 and its epilogue (bias, GELU) runs in float32.  The residual streams (encoder / DConv, LayerScale),
+    # the GroupNorm / LayerNorm statistics and outputs that no product reads, the GLUs, the transposed-convolution fold, the input
+    # normalisation, STFT / iSTFT and the output stages are float32.  A batch runs as B images / sequences / groups in every launch.
+    def _conv_h(self, x: torch.Tensor, B: int, H: int, W: int, cv: _Conv, stride=(1, 1), pad=(0, 0), dil=(1, 1), act=ACT_NONE,
+                out_f16: bool = False, Hv: Optional[int] = None, bias: bool = True) -> Tuple[torch.Tensor, int, int]:
+        """x [B, Hv, W, cin] (half or float32; rows Hv .. H - 1 read as zeros) -> (y [B Ho Wo, cout], Ho, Wo) on the f16 pipe"""
+        ctx = self.ctx
+        Ho = (H + 2 * pad[0] - dil[0] * (cv.kh - 1) - 1) // stride[0] + 1
+        Wo = (W + 2 * pad[1] - dil[1] * (cv.kw - 1) - 1) // stride[1] + 1
+        y = ctx.empty((B * Ho * Wo, cv.cout), torch.float16 if out_f16 else torch.float32)
+        ctx.check(ctx.lib.alsep_nn_conv_h(ctx.handle, _lib.ptr(x), 1 if x.dtype == torch.float16 else 0, _lib.ptr(cv.wh),
+                                          _lib.ptr(cv.shift) if bias else None, _lib.ptr(y), 1 if out_f16 else 0, cv.cout, B, H,
+                                          Hv if Hv is not None else H, W, cv.cin, cv.cin, cv.cout, cv.kp, cv.kh, cv.kw, stride[0], stride[1],
+                                          pad[0], pad[1], dil[0], dil[1], act), "alsep_nn_conv_h")
+        return y, Ho, Wo
+
+    def _lin_h(self, a: torch.Tensor, B: int, N: int, cv: _Conv, act=ACT_NONE, out_f16: bool = False) -> torch.Tensor:
+        """a [B, N, K] IEEE half -> [B N, cout] = act(a W^T + bias) on alsep_nn_gemm_f16, one GEMM per sample (batch-invariant)"""
+        ctx = self.ctx
+        K, No = cv.cin, cv.cout
+        y = ctx.empty((B * N, No), torch.float16 if out_f16 else torch.float32)
+        ctx.check(ctx.lib.alsep_nn_gemm_f16(ctx.handle, _lib.ptr(a), K, N * K, _lib.ptr(cv.wh), cv.kp, 0, _lib.ptr(y), 1 if out_f16 else 0, No,
+                                            N * No, _lib.ptr(cv.shift), 0, None, 0, 0, B, N, No, K, 1.0, act, None), "alsep_nn_gemm_f16")
+        return y
+
+    def _norm_h(self, x: torch.Tensor, G: int, R: int, Cn: int, gamma, beta, act=ACT_NONE, out_f16: bool = False) -> torch.Tensor:
+        ctx = self.ctx
+        need = int(ctx.lib.alsep_nn_norm_h_workspace_bytes(G, R * Cn))
+        if self._ws_h is None or self._ws_h.numel() < need:
+            self._ws_h = ctx.empty((max(need, 1 << 16),), torch.uint8)
+        y = ctx.empty((G * R, Cn // 2 if act == ACT_GLU else Cn), torch.float16 if out_f16 else torch.float32)
+        ctx.check(ctx.lib.alsep_nn_norm_h(ctx.handle, _lib.ptr(x), _lib.ptr(y), 1 if out_f16 else 0, _lib.ptr(gamma), _lib.ptr(beta), G, R, Cn,
+                                          1e-5, act, _lib.ptr(self._ws_h)), "alsep_nn_norm_h")
+        return y
+
+    def _dconv_h(self, y: torch.Tensor, B: int, H: int, W: int, Cn: int, layers, freq: bool) -> torch.Tensor:
+        rows = B * H * W
+        G, R = (B * H, W) if freq else (B, H)
+        for L in layers:
+            d = L["dil"]
+            h, _, _ = self._conv_h(y, B, H, W, L["c1"], pad=(0, d) if freq else (d, 0), dil=(1, d) if freq else (d, 1))
+            h = self._norm_h(h, G, R, L["c1"].cout, L["g1"], L["b1"], ACT_GELU, out_f16=True)
+            h, _, _ = self._conv_h(h, B, H, W, L["c2"])
+            h = self._norm_h(h, G, R, L["c2"].cout, L["g2"], L["b2"], ACT_GLU)
+            y = self._scale_add(y, h, L["scale"], rows, Cn)
+        return y
+
+    def _enc_layer_h(self, x: torch.Tensor, B: int, H: int, W: int, P, freq: bool, Hv: Optional[int] = None):
+        cfg = self.cfg
+        cv = P["conv"]
+        y, Ho, Wo = self._conv_h(x, B, H, W, cv, stride=(cfg.stride, 1), pad=(cfg.kernel_size // 4, 0), act=ACT_GELU, Hv=Hv)
+        y = self._dconv_h(y, B, Ho, Wo, cv.cout, P["dconv"], freq)
+        z, _, _ = self._conv_h(y, B, Ho, Wo, P["rewrite"])
+        return self._act(z, B * Ho * Wo, 2 * cv.cout, ACT_GLU), Ho
+
+    def _dec_layer_h(self, x: torch.Tensor, skip: torch.Tensor, B: int, H: int, W: int, P, freq: bool, length: int, last: bool):
+        ctx, cfg = self.ctx, self.cfg
+        cin = P["rewrite"].cin
+        rows = B * H * W
+        x = self._scale_add(x, skip, None, rows, cin)
+        r, _, _ = self._conv_h(x, B, H, W, P["rewrite"], pad=(cfg.context, cfg.context if freq else 0))
+        y = self._act(r, rows, 2 * cin, ACT_GLU)
+        g, _, _ = self._conv_h(y, B, H, W, P["tr"], bias=False)
+        z = ctx.empty((B * length * W, P["cout"]))
+        ctx.check(ctx.lib.alsep_nn_tconv_fold(ctx.handle, _lib.ptr(g), _lib.ptr(P["bias"]), _lib.ptr(z), B, H, W, P["cout"], cfg.stride,
+                                              cfg.kernel_size // 4, length, ACT_NONE if last else ACT_GELU), "alsep_nn_tconv_fold")
+        return z
+
+    def _tlayer_h(self, x: torch.Tensor, B: int, N: int, other: Optional[torch.Tensor], No: int, P) -> torch.Tensor:
+        ctx, cfg = self.ctx, self.cfg
+        Cd, Hh = cfg.bottom_channels, cfg.t_heads
+        a = ctx.empty((B * N, Cd), torch.float16)
+        if not P["cross"]:
+            h = self._norm_h(x, B * N, 1, Cd, *P["norm1"], out_f16=True)
+            qkv = self._lin_h(h, B, N, P["wqkv"], out_f16=True)
+            ctx.check(ctx.lib.alsep_nn_attention_f16(ctx.handle, _lib.ptr(qkv), _lib.ptr(a), B, N, Hh, 64, N * 3 * Cd, 3 * Cd, N * Cd, Cd, 0.125,
+                                                     None, None, 0, 0), "alsep_nn_attention_f16")
+        else:
+            q = self._lin_h(self._norm_h(x, B * N, 1, Cd, *P["norm1"], out_f16=True), B, N, P["wq"], out_f16=True)
+            kv = self._lin_h(self._norm_h(other, B * No, 1, Cd, *P["norm2"], out_f16=True), B, No, P["wkv"], out_f16=True)
+            ctx.check(ctx.lib.alsep_nn_xattention_f16(ctx.handle, _lib.ptr(q), _lib.ptr(kv), _lib.ptr(a), B, N, No, Hh, 64, N * Cd, Cd, No * 2 * Cd,
+                                                      2 * Cd, N * Cd, Cd, 0.125), "alsep_nn_xattention_f16")
+        a = self._lin_h(a, B, N, P["out"])
+        x = self._scale_add(x, a, P["g1"], B * N, Cd)
+        h = self._norm_h(x, B * N, 1, Cd, *(P["norm3"] if P["cross"] else P["norm2"]), out_f16=True)
+        f = self._lin_h(h, B, N, P["l1"], act=ACT_GELU, out_f16=True)
+        f = self._lin_h(f, B, N, P["l2"])
+        x = self._scale_add(x, f, P["g2"], B * N, Cd)
+        return self._norm_h(x, B, N, Cd, *P["norm_out"])
+
+    def _meanstd_b(self, x: torch.Tensor, B: int, n: int) -> torch.Tensor:
+        """per-sample (mean, unbiased std) of B samples of n values: one reduction per sample, so a sample's statistics do not depend on B"""
+        ctx = self.ctx
+        stats = ctx.empty((B, 2))
+        ws = self._workspace(1, n)
+        for b in range(B):
+            ctx.check(ctx.lib.alsep_nn_meanstd(ctx.handle, C.c_void_p(x.data_ptr() + 4 * b * n), 1, n, C.c_void_p(stats.data_ptr() + 8 * b),
+                                               _lib.ptr(ws)), "alsep_nn_meanstd")
+        return stats
+
+    def _forward_h(self, mix: torch.Tensor) -> torch.Tensor:
+        ctx, cfg = self.ctx, self.cfg
+        lib, h = ctx.lib, ctx.handle
+        single = mix.dim() == 2
+        if single:
+            mix = mix[None]
+        if mix.dim() != 3 or mix.shape[1] != 2 or mix.dtype != torch.float32:
+            raise AlsepError("HTDemucs.forward expects a float32 [2, L] or [B, 2, L] tensor")
+        B = int(mix.shape[0])
+        length_pre_pad = None
+        if mix.shape[-1] < cfg.segment_samples:
+            length_pre_pad = mix.shape[-1]
+            padded = ctx.zeros((B, 2, cfg.segment_samples))
+            padded[..., :length_pre_pad] = mix
+            mix = padded
+        mix = mix.contiguous()
+        L = mix.shape[-1]
+        hl, nfft, S = cfg.hop, cfg.nfft, cfg.S
+        le = -(-L // hl)
+        pad = hl // 2 * 3
+        Lp = le * hl + 2 * pad
+        xp = ctx.empty((B, 2, Lp))
+        ctx.check(lib.alsep_nn_reflect_pad(h, _lib.ptr(mix), _lib.ptr(xp), 2 * B, L, pad, pad + le * hl - L), "alsep_nn_reflect_pad")
+        Tt, Fq = le + 4, nfft // 2
+        plan = self._plan(Tt)
+        spec = plan.stft_strided(xp, Lp, 2 * Lp, B, torch.float32, _lib.LAYOUT_REF)            # [B, 4, Fq, Tt]
+        n = Fq * le * 4
+        x = ctx.empty((B * Fq * le, 4))
+        ctx.check(lib.alsep_demucs_spec_in(h, _lib.ptr(spec), _lib.ptr(x), B, Fq, Tt, le, 2, 1.0 / math.sqrt(nfft)), "alsep_demucs_spec_in")
+        stats = self._meanstd_b(x, B, n)
+        xn = torch.empty_like(x)
+        ctx.check(lib.alsep_nn_affine_stats(h, _lib.ptr(x), _lib.ptr(xn), _lib.ptr(stats), B, n, 1e-5, 0), "alsep_nn_affine_stats")
+        x = xn
+        xt = ctx.empty((B * L, 2))
+        ctx.check(lib.alsep_nn_swap_last2(h, _lib.ptr(mix), _lib.ptr(xt), B, 2, L), "alsep_nn_swap_last2")
+        stats_t = self._meanstd_b(xt, B, 2 * L)
+        xtn = torch.empty_like(xt)
+        ctx.check(lib.alsep_nn_affine_stats(h, _lib.ptr(xt), _lib.ptr(xtn), _lib.ptr(stats_t), B, 2 * L, 1e-5, 0), "alsep_nn_affine_stats")
+        xt = xtn
+
+        saved, saved_t, lengths_t = [], [], []
+        Fr, Lt = Fq, L
+        St = cfg.stride
+        for idx in range(cfg.depth):
+            lengths_t.append(Lt)
+            Lin = -(-Lt // St) * St                             # zero-padded on the right to a multiple of the stride (rows >= Lt read 0)
+            xt, Lt = self._enc_layer_h(xt, B, Lin, 1, self.tenc[idx], freq=False, Hv=Lt)
+            saved_t.append((xt, Lt))
+            x, Fr = self._enc_layer_h(x, B, Fr, le, self.enc[idx], freq=True)
+            if idx == 0:
+                c0 = self.enc[0]["conv"].cout
+                ctx.check(lib.alsep_nn_add_bcast(h, _lib.ptr(x), _lib.ptr(self.freq_emb), cfg.freq_emb, B * Fr * le * c0, le * c0, Fr, c0),
+                          "alsep_nn_add_bcast")
+            saved.append((x, Fr))
+        Cd = cfg.bottom_channels
+        N1, N2 = Fr * le, Lt
+        x, _, _ = self._conv_h(x, B, N1, 1, self.up)
+        xt, _, _ = self._conv_h(xt, B, N2, 1, self.up_t)
+        e2d, e1d = self._pos_tables(Fr, le, N2)
+        x = self._norm_h(x, B * N1, 1, Cd, *self.norm_in)
+        ctx.check(lib.alsep_nn_add_bcast(h, _lib.ptr(x), _lib.ptr(e2d), cfg.t_weight_pos_embed, B * N1 * Cd, Cd, N1, Cd), "alsep_nn_add_bcast")
+        xt = self._norm_h(xt, B * N2, 1, Cd, *self.norm_in_t)
+        ctx.check(lib.alsep_nn_add_bcast(h, _lib.ptr(xt), _lib.ptr(e1d), cfg.t_weight_pos_embed, B * N2 * Cd, Cd, N2, Cd), "alsep_nn_add_bcast")
+        for idx in range(cfg.t_layers):
+            if idx % 2 == 0:
+                x = self._tlayer_h(x, B, N1, None, 0, self.layers[idx])
+                xt = self._tlayer_h(xt, B, N2, None, 0, self.layers_t[idx])
+            else:
+                old_x = x
+                x = self._tlayer_h(x, B, N1, xt, N2, self.layers[idx])
+                xt = self._tlayer_h(xt, B, N2, old_x, N1, self.layers_t[idx])
+        x, _, _ = self._conv_h(x, B, N1, 1, self.down)
+        xt, _, _ = self._conv_h(xt, B, N2, 1, self.down_t)
+        for idx in range(cfg.depth):
+            last = idx == cfg.depth - 1
+            skip, Fs = saved.pop(-1)
+            x = self._dec_layer_h(x, skip, B, Fs, le, self.dec[idx], True, Fs * cfg.stride, last)
+            skip_t, Ls = saved_t.pop(-1)
+            xt = self._dec_layer_h(xt, skip_t, B, Ls, 1, self.tdec[idx], False, lengths_t.pop(-1), last)
+        spec_out = ctx.empty((B * S, 4, Fq, Tt))
+        ctx.check(lib.alsep_demucs_spec_out(h, _lib.ptr(x), _lib.ptr(stats), _lib.ptr(spec_out), B, S, Fq, Tt, le, 2, math.sqrt(nfft)),
+                  "alsep_demucs_spec_out")
+        xs = ctx.empty((B * S, 2, L))
+        plan.istft_strided(spec_out, _lib.LAYOUT_REF, xs, L, 2 * L, pad, pad + L, (B * S - 1) * 2 * L + L)
+        out = ctx.empty((B, S, 2, L))
+        ctx.check(lib.alsep_demucs_mix_out(h, _lib.ptr(xt), _lib.ptr(stats_t), _lib.ptr(xs), _lib.ptr(out), B, S, L), "alsep_demucs_mix_out")
+        if length_pre_pad:
+            out = out[..., :length_pre_pad]
+        return out[0] if single else out
+
     __call__ = forward
+
+
+# units per batched forward of a half-precision network in DemucsRunner (ALSEP_DEMUCS_BATCH overrides).  Measured, htdemucs_6s 10 min
+# (profiles/demucs_half_batch_sweep.txt): batch 1 1.38 s, 2 0.97 s, 4 0.76 s, 8 0.70 s
+DEFAULT_F16_BATCH = 8
 
 
 def shift_offsets(shifts: int, max_shift: int, seed: int = 0) -> List[int]:
@@ -550,7 +787,8 @@ class DemucsRunner:
     ``est[s] = sum_m w[m][s] out_m[s] / sum_m w[m][s]`` (demucs 4 apply.py, restated -- PARITY UNPINNED)."""
 
     def __init__(self, net, shifts: int = 2, overlap: float = 0.25, seed: int = 0, sharded: bool = False, group=None,
-                 lanes: Optional[int] = None, graphs: Optional[bool] = None, contraction: str = "exact", weights=None):
+                 lanes: Optional[int] = None, graphs: Optional[bool] = None, contraction: str = "exact", weights=None,
+                 batch: Optional[int] = None):
         """``lanes``: (shift, segment) units in flight at once, each on a HIP stream of its own (default: 4 on a GPU, 1 elsewhere).  One
         segment of htdemucs_6s is ~450 launches of mostly small kernels (grids of 42-170 workgroups on 256 CUs): units are independent,
         so running a few side by side fills the chip; the weighted sums are kept per lane and added at the end."""
@@ -565,6 +803,10 @@ class DemucsRunner:
                                  f"{n.cfg.audio_channels})")
             if n.ctx is not nets[0].ctx:
                 raise AlsepError("DemucsRunner: the members of a bag must share one context")
+        precisions = {getattr(n, "precision", "f32") for n in nets}
+        if len(precisions) > 1:
+            raise AlsepError(f"DemucsRunner: the members of a bag must share one precision, not {sorted(precisions)}")
+        self.precision = precisions.pop()
         from .th_reader import bag_weights
         self.nets = nets
         self.weights = bag_weights(weights, len(nets), first.S, "DemucsRunner")
@@ -579,6 +821,21 @@ class DemucsRunner:
         self.contraction = contraction
         if contraction == "split":
             lanes = 1          # the split kernels issue f16 MFMA: FFT launches must not share the GPU with them (roformer.RoformerRunner)
+        # Half-precision networks (HTDemucs(precision="f16")) issue f16 MFMA too: ONE lane, no graphs, and the units of
+        # one member run ``batch`` at a time through the batched forward (every launch then covers that many segments).  float32 networks
+        # keep batch 1, their lanes and graphs.
+        self.batch = 1
+        if self.precision == "f16":
+            if contraction == "split":
+                raise AlsepError("DemucsRunner: contraction='split' is a float32-network mode")
+            if lanes is not None and int(lanes) > 1:
+                import logging
+                logging.getLogger(__name__).info("DemucsRunner: half-precision networks run on one lane (DESIGN section 6), not %d", int(lanes))
+            lanes, graphs = 1, False
+            self.batch = max(1, int(batch if batch is not None else os.environ.get("ALSEP_DEMUCS_BATCH", str(DEFAULT_F16_BATCH))))
+        self.batches_run = 0                                   # batched forwards of the last track (half-precision networks)
+        self._f32_rerun = False
+        self._f32_nets: Dict[int, "HTDemucs"] = {}
         self.shifts, self.overlap, self.seed = shifts, overlap, seed
         self.sharded, self.group = sharded, group
         if lanes is None:
@@ -660,6 +917,8 @@ class DemucsRunner:
 
     def separate(self, mix: torch.Tensor) -> Dict[str, torch.Tensor]:
         """mix [2, L] on the device -> {source name: [2, L]} (sources in the model's order)"""
+        if self.precision == "f16":
+            return self._separate_f16(mix)
         if self.contraction != "split":
             return self._separate(mix)
         ctxs = [self.ctx] + [lnets[0].ctx for lnets, _ in self._lanes() if lnets[0].ctx is not self.ctx]
@@ -684,6 +943,33 @@ class DemucsRunner:
                                                 "again on the exact float32 kernels")
             self._graphs.clear()                               # captured with the split kernels
             out = self._separate(mix)
+        return out
+
+    @staticmethod
+    def _stems_finite(out: Dict[str, torch.Tensor]) -> bool:
+        """the overflow check of the half-precision mode (a host hook: tests replace it to force the float32 re-run)"""
+        return all(bool(torch.isfinite(v).all()) for v in out.values())
+
+    def _separate_f16(self, mix: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """the half-precision networks; a track whose stems are not all finite (an activation beyond the half range) is run again on
+        the float32 weights, with a WARNING.  Sharded: the decision is agreed by every rank first (all_reduce MAX)."""
+        self._f32_rerun = False
+        out = self._separate(mix)
+        bad = not self._stems_finite(out)
+        if self.sharded:
+            import torch.distributed as tdist
+            flag = torch.tensor([1 if bad else 0], dtype=torch.int32, device=self.ctx.device)
+            tdist.all_reduce(flag, op=tdist.ReduceOp.MAX, group=self.group)
+            bad = bool(int(flag.item()))
+        if bad:
+            import logging
+            logging.getLogger(__name__).warning("DemucsRunner: the half-precision stems of this track are not all finite -- running it "
+                                                "again in float32")
+            self._f32_rerun = True
+            try:
+                out = self._separate(mix)
+            finally:
+                self._f32_rerun = False
         return out
 
     def _separate(self, mix: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -739,7 +1025,43 @@ class DemucsRunner:
                 dst = C.c_void_p(lane_acc[v].data_ptr() + 4 * (j0 * 2 * width + off))
                 lctx.check(lctx.lib.alsep_nn_vec_fma(lctx.handle, dst, src, _lib.ptr(tri[seg]), n * 2, cl, width, seg), "alsep_nn_vec_fma")
 
-        for i, unit in enumerate(units[lo:hi]):
+        def run_batch(batch_units):
+            """half-precision networks: up to ``batch`` units of one member as one batched forward on lane 0"""
+            vw0 = views[batch_units[0][0]]
+            seg = vw0.seg
+            net_m = self.nets[vw0.m]
+            chunks = ctx.zeros((len(batch_units), 2, seg))
+            for b, (v, offset, view_len, off, cl) in enumerate(batch_units):
+                delta = seg - cl
+                start = offset + off - delta // 2
+                cs, ce = max(0, start), min(total, start + seg)
+                chunks[b, :, cs - start: cs - start + (ce - cs)] = root[:, cs:ce]
+            if self._f32_rerun:
+                net32 = self._f32_nets.setdefault(vw0.m, net_m.as_f32())
+                ys = [net32.forward(chunks[b]) for b in range(len(batch_units))]
+            else:
+                yb = net_m.forward(chunks)                                               # [B, S, 2, seg]
+                ys = [yb[b] for b in range(len(batch_units))]
+                self.batches_run += 1
+            for (v, offset, view_len, off, cl), y in zip(batch_units, ys):
+                vw = views[v]
+                delta = seg - cl
+                for s0, n, j0 in vw.runs:
+                    src = C.c_void_p(y.data_ptr() + 4 * (s0 * 2 * seg + delta // 2))
+                    dst = C.c_void_p(accs[0][v].data_ptr() + 4 * (j0 * 2 * width + off))
+                    ctx.check(lib.alsep_nn_vec_fma(h, dst, src, _lib.ptr(tri[seg]), n * 2, cl, width, seg), "alsep_nn_vec_fma")
+
+        if self.precision == "f16":
+            self.batches_run = 0
+            pending: List[tuple] = []
+            for unit in units[lo:hi]:
+                if pending and (len(pending) == self.batch or views[unit[0]].m != views[pending[0][0]].m):
+                    run_batch(pending)
+                    pending = []
+                pending.append(unit)
+            if pending:
+                run_batch(pending)
+        for i, unit in enumerate(units[lo:hi] if self.precision != "f16" else []):
             k = i % len(lanes)
             lane_nets, st = lanes[k]
             if st is None:

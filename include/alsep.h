@@ -77,7 +77,9 @@ enum {
     ALSEP_PROF_NN_CONV = 13,     /* nn_conv2d_tiled_kernel / vr_conv2d_kernel through alsep_nn_conv2d */
     ALSEP_PROF_NN_GEMM_H = 14,   /* nn_gemm_h_kernel (f16 MFMA Linear) */
     ALSEP_PROF_NN_ATTN_H = 15,   /* nn_attn_h_kernel (one-pass f16 attention) */
-    ALSEP_PROF_NN_CONV_H = 16    /* nn_conv_hh_kernel (f16 MFMA convolution) + its split-K reduction */
+    ALSEP_PROF_NN_CONV_H = 16,   /* nn_conv_hh_kernel (f16 MFMA convolution) + its split-K reduction */
+    ALSEP_PROF_NN_DCONV_H = 17,  /* nn_dconv_h_kernel (f16 MFMA convolution of HTDemucs' half-precision mode) */
+    ALSEP_PROF_NN_NORM_H = 18    /* nn_norm_h_* (GroupNorm / LayerNorm to half: statistics, final, apply) */
 };
 int alsep_profile_begin(alsep_ctx* ctx, int category);
 int alsep_profile_end(alsep_ctx* ctx, double* total_ms, int64_t* launches);
@@ -418,6 +420,22 @@ int alsep_nn_gemm_f16(alsep_ctx* ctx, const void* A, int64_t lda, int64_t sa_b, 
 int alsep_nn_attention_f16(alsep_ctx* ctx, const void* qkv, void* out, int n_seq, int L, int heads, int dim_head, int64_t seq_stride,
                            int64_t row_stride, int64_t o_seq_stride, int64_t o_row_stride, float scale, const float* rot_table,
                            const float* gates, int64_t g_seq_stride, int64_t g_row_stride);
+/* HTDemucs half-precision mode (csrc/nn_demucs_h.h).
+ * Convolution on the f16 matrix pipe for Demucs geometries: x channels-last [B, Hv, W, x_ld] (x_f16: IEEE half, else float32 rounded to
+ * half as it is read; rows Hv .. H - 1 of an image read as zeros), w [Cout][Kp] IEEE half, k = (dy, dx, ci) zero-padded from KH KW Cin to
+ * Kp (a multiple of 32); y [B, Ho, Wo] pixels y_ld elements apart = act(conv + bias), act 0 or 3 (GELU), half (y_f16) or float32. */
+int alsep_nn_conv_h(alsep_ctx* ctx, const void* x, int x_f16, const void* w, const float* bias, void* y, int y_f16, int64_t y_ld, int64_t B,
+                    int H, int Hv, int W, int x_ld, int Cin, int Cout, int Kp, int KH, int KW, int stride_h, int stride_w, int pad_h, int pad_w,
+                    int dil_h, int dil_w, int act);
+/* bytes of device scratch (8-byte aligned) for alsep_nn_norm_h over G groups of per_group elements */
+int64_t alsep_nn_norm_h_workspace_bytes(int64_t G, int64_t per_group);
+/* alsep_nn_norm with the result stored as IEEE half (y_f16) or float32; the statistics of a group do not depend on G */
+int alsep_nn_norm_h(alsep_ctx* ctx, const float* x, void* y, int y_f16, const float* gamma, const float* beta, int64_t G, int64_t R, int C,
+                    float eps, int act, void* workspace);
+/* cross-attention in half: q [n_seq][Lq] rows, kv [n_seq][Lk] rows of k (heads x 64) | v (heads x 64); out [n_seq][Lq] rows, IEEE half */
+int alsep_nn_xattention_f16(alsep_ctx* ctx, const void* q, const void* kv, void* out, int n_seq, int Lq, int Lk, int heads, int dim_head,
+                            int64_t q_seq_stride, int64_t q_row_stride, int64_t kv_seq_stride, int64_t kv_row_stride, int64_t o_seq_stride,
+                            int64_t o_row_stride, float scale);
 /* Roformer band split, input side, all bands in one launch: feat[band][t][kmax] (half) = RMSNorm over the band's `width[band]` gathered
  * spectrogram values of frame t (spec [4][F][T]; pidx[band][kmax / 2] merged bin index 2 f + s or -1; gamma[band][kmax]), zero-padded */
 int alsep_roformer_bandsplit_in(alsep_ctx* ctx, const float* spec, const int* pidx, const float* gamma, const int* width, void* feat, int nb,
