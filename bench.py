@@ -11,6 +11,12 @@ segments are all-gathered once per model (RCCL), so per-GPU work is fixed ("weak
 
 python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed steps, --dump-outputs if asked, the
+line.  --full adds everything else after the timed steps, each from runs of its own: the roofline of the dominant 3x3-conv
+class (its launches bracketed by HIP events during the timed steps, as the class is picked by one untimed pass per class
+before them), the other conv classes and the STFT / iSTFT stages, the other storage types with their accuracy, the CPU
+baseline and, at N > 1, the other scaling mode.
 """
 from __future__ import annotations
 
@@ -422,7 +428,7 @@ def other_workload(args) -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t[0])
     roofline = cpu = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         run_once = make_prof()
         run_once()                                             # builds the one-lane engine's plans / workspaces
         fence()
@@ -431,14 +437,16 @@ def other_workload(args) -> None:
             cpu = cpu_fn()
     if rank == 0:
         mult = 4 if wl == "longform" else 1                    # stereo pairs count as separate 2-channel programmes
-        print(json.dumps({
+        line = {
             "metric": "stems*realtime-factor (44.1kHz stereo)", "value": round(stems * mult * audio_s * args.steps / dt, 2),
             "unit": "stems*x_realtime", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": dtype_name, "data": "synthetic",
             "config": {"workload": desc, "stems": stems, "audio_seconds": audio_s, "sample_rate": sr, "sharding": sharding},
-            "realtime_factor": round(mult * audio_s * args.steps / dt, 2),
-            "roofline": roofline, "cpu_baseline": cpu}), flush=True)
+            "realtime_factor": round(mult * audio_s * args.steps / dt, 2), "full": args.full}
+        if args.full:
+            line.update({"roofline": roofline, "cpu_baseline": cpu})
+        print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -479,14 +487,18 @@ def main() -> None:
                     help="model windows per network launch (0 = all of a rank's windows in one launch, at most 64: 18 GiB of workspace per "
                          "model at 52 windows; profiles/r02_batch_sweep.txt: 8 -> 220, 16 -> 216, 26 -> 212, 52 -> 207 ms per step)")
     ap.add_argument("--seconds", type=int, default=TRACK_SECONDS, help="audio seconds per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline, per-kernel and per-stage figures, the other storage types and "
+                         "their accuracy, the CPU baseline and (N > 1) the other scaling mode; a plain run prints the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the `cpu_baseline` object")
     ap.add_argument("--no-precision", action="store_true",
-                    help="skip the `precision` / `accuracy` objects (full steps in the other storage types after the timed region; N = 1 only)")
-    ap.add_argument("--cpu-windows", type=int, default=2)
+                    help="with --full: skip the `precision` / `accuracy` objects (full steps in the other storage types after the timed "
+                         "region; N = 1 only)")
+    ap.add_argument("--cpu-windows", type=int, default=2, help="with --full: model windows of the CPU baseline's sample")
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
                     help="strong (default): the --seconds track in total, its model windows sharded over the N GPUs -- what 'scaling to 8 GPUs' "
                          "means for one track (52 windows: 6-7 per rank at N = 8); weak: N x --seconds of audio on N GPUs (per-GPU work fixed). "
-                         "At N > 1 the line carries the other mode too (`other_scaling`), measured after the timed region.")
+                         "With --full at N > 1 the line carries the other mode too (`other_scaling`), measured after the timed region.")
     ap.add_argument("--model", default="vocals_mel_band_roformer.ckpt", help="roster name of the model workload")
     ap.add_argument("--workload", default="mdx4", choices=["mdx4", "demucs6", "tracks", "longform", "model"],
                     help="mdx4 (default): BASELINE configs[1], the graded line.  Supplementary lines for the other configs: demucs6 = "
@@ -556,32 +568,34 @@ def main() -> None:
         stems = step()
     fence()
     half = dtype in (torch.bfloat16, torch.float16)          # the f16 build runs the same kernels (tdfnet_f16.hip)
-    klevels = conv_kernel_levels(cfg, half, args.batch)
-    KCAT = {"big": _lib.PROF_CONV3X3_BIG, "big3": _lib.PROF_CONV3X3_BIG3, "regw": _lib.PROF_CONV3X3_REGW, "plain": _lib.PROF_CONV3X3}
-    # the dominant kernel = the 3x3 class with the largest share of a step: one untimed pass per class decides which one the HIP
-    # events bracket during the timed steps
-    share = {}
-    for cls in KCAT:
-        if klevels[cls]:
-            ctx.profile_begin(KCAT[cls])
-            step()
-            fence()
-            share[cls] = ctx.profile_end()[0]
-    # the level-1 class has three kernels behind one profiling category: report the one that ran (launch counts by name)
-    big_name = next((n for n in ("conv3x3_bf16_mq_kernel", "conv3x3_bf16_mny_kernel<2>") if ctx.launch_count(n) > 0),
-                    "conv3x3_bf16_big_kernel<2>")
-    big3_name = "conv3x3_bf16_mny_kernel<3>" if ctx.launch_count("conv3x3_bf16_mny_kernel<3>") > 0 else "conv3x3_bf16_big_kernel<3>"
-    l0_name = "conv3x3_bf16_m0_kernel" if ctx.launch_count("conv3x3_bf16_m0_kernel") > 0 else "conv3x3_bf16_regw_kernel<1>"
-    KCLASS = {"big": (big_name, KCAT["big"]), "big3": (big3_name, KCAT["big3"]), "regw": (l0_name, KCAT["regw"]),
-              "plain": ("conv3x3_bf16_kernel<64>" if half else "conv3x3_kernel<f32,16,48,64>", KCAT["plain"])}
-    primary = max(share, key=share.get) if share else "plain"
-    ctx.profile_begin(KCLASS[primary][1])
+    if args.full:
+        klevels = conv_kernel_levels(cfg, half, args.batch)
+        KCAT = {"big": _lib.PROF_CONV3X3_BIG, "big3": _lib.PROF_CONV3X3_BIG3, "regw": _lib.PROF_CONV3X3_REGW, "plain": _lib.PROF_CONV3X3}
+        # the dominant kernel = the 3x3 class with the largest share of a step: one untimed pass per class decides which one the HIP
+        # events bracket during the timed steps
+        share = {}
+        for cls in KCAT:
+            if klevels[cls]:
+                ctx.profile_begin(KCAT[cls])
+                step()
+                fence()
+                share[cls] = ctx.profile_end()[0]
+        # the level-1 class has three kernels behind one profiling category: report the one that ran (launch counts by name)
+        big_name = next((n for n in ("conv3x3_bf16_mq_kernel", "conv3x3_bf16_mny_kernel<2>") if ctx.launch_count(n) > 0),
+                        "conv3x3_bf16_big_kernel<2>")
+        big3_name = "conv3x3_bf16_mny_kernel<3>" if ctx.launch_count("conv3x3_bf16_mny_kernel<3>") > 0 else "conv3x3_bf16_big_kernel<3>"
+        l0_name = "conv3x3_bf16_m0_kernel" if ctx.launch_count("conv3x3_bf16_m0_kernel") > 0 else "conv3x3_bf16_regw_kernel<1>"
+        KCLASS = {"big": (big_name, KCAT["big"]), "big3": (big3_name, KCAT["big3"]), "regw": (l0_name, KCAT["regw"]),
+                  "plain": ("conv3x3_bf16_kernel<64>" if half else "conv3x3_kernel<f32,16,48,64>", KCAT["plain"])}
+        primary = max(share, key=share.get) if share else "plain"
+        ctx.profile_begin(KCLASS[primary][1])
     t0 = time.perf_counter()
     for _ in range(args.steps):
         stems = step()
     fence()
     dt = time.perf_counter() - t0
-    conv_ms, conv_launches = ctx.profile_end()
+    if args.full:
+        conv_ms, conv_launches = ctx.profile_end()
     if world > 1:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -589,6 +603,39 @@ def main() -> None:
     assert stems[0].shape == (1, 2, n_samples) and bool(torch.isfinite(stems[0]).all())
     if args.dump_outputs and rank == 0:                     # before any untimed pass below can reuse a buffer
         dump_outputs(args.dump_outputs, {f"stem{i}": s for i, s in enumerate(stems)})
+
+    def headline(**extra):
+        audio_seconds = n_samples / SR
+        return {
+            "metric": "stems*realtime-factor (44.1kHz stereo)",
+            "value": round(N_STEMS * audio_seconds * args.steps / dt, 2),
+            "unit": "stems*x_realtime",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 2),
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": args.dtype,
+            "data": "synthetic",
+            "config": {"workload": f"MDX-Net UVR 4-stem (4x TFC-TDF U-Net L=11 g=48 dim_f=3072 dim_t=256 n_fft=6144), "
+                                   f"{args.seconds} s 44.1 kHz stereo {'per GPU' if args.scaling == 'weak' and world > 1 else 'in total'}, margin chunker, "
+                                   f"windows/launch={args.batch}",
+                       "stems": N_STEMS, "audio_seconds": audio_seconds, "sharding": f"windows/{world} + all_gather"},
+            "realtime_factor_4stem": round(audio_seconds * args.steps / dt, 2),
+            "full": args.full,
+            **extra,
+        }
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # the other scaling mode, after the timed region (N > 1 only; at N = 1 the two coincide): same models, the other track length
     other_scaling = None
     if world > 1:
@@ -816,35 +863,8 @@ def main() -> None:
             torch.cuda.empty_cache()
 
     if rank == 0:
-        audio_seconds = n_samples / SR
-        value = N_STEMS * audio_seconds * args.steps / dt
-        line = {
-            "metric": "stems*realtime-factor (44.1kHz stereo)",
-            "value": round(value, 2),
-            "unit": "stems*x_realtime",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 2),
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic",
-            "config": {"workload": f"MDX-Net UVR 4-stem (4x TFC-TDF U-Net L=11 g=48 dim_f=3072 dim_t=256 n_fft=6144), "
-                                   f"{args.seconds} s 44.1 kHz stereo {'per GPU' if args.scaling == 'weak' and world > 1 else 'in total'}, margin chunker, "
-                                   f"windows/launch={args.batch}",
-                       "stems": N_STEMS, "audio_seconds": audio_seconds, "sharding": f"windows/{world} + all_gather"},
-            "realtime_factor_4stem": round(audio_seconds * args.steps / dt, 2),
-            "roofline": roofline,
-            "kernels": other,
-            "stages": stages,
-            "precision": precision,
-            "accuracy": accuracy,
-            "cpu_baseline": cpu,
-            "other_scaling": other_scaling,
-        }
-        print(json.dumps(line), flush=True)
+        print(json.dumps(headline(roofline=roofline, kernels=other, stages=stages, precision=precision, accuracy=accuracy,
+                                  cpu_baseline=cpu, other_scaling=other_scaling)), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -1,21 +1,22 @@
 #!/bin/bash
 # Round-3 evidence, call A: PMC traffic (two passes; the bench line reads the resulting file, stamped with the kernel-source hash) and SQ counters.
 set -u
+OUT="${OUT:-out}"
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-mkdir -p gpurun_out
+mkdir -p $OUT
 export TMPDIR=/tmp
 rm -rf /tmp/pmc
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 500 rocprofv3 --pmc $c --output-format csv -d /tmp/pmc/$c -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-precision > gpurun_out/pmc_$c.log 2>&1
+  timeout -k 10 500 rocprofv3 --pmc $c --output-format csv -d /tmp/pmc/$c -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-precision > $OUT/pmc_$c.log 2>&1
   echo "pmc $c rc=$?"
 done
 python scripts/pmc_summary.py /tmp/pmc > /dev/null
-W=$(grep -o 'windows/launch=[0-9]*' gpurun_out/pmc_FETCH_SIZE.log | tail -1 | cut -d= -f2)
-python scripts/pmc_traffic.py /tmp/pmc/pmc_summary.json gpurun_out/pmc_traffic.json ${W:-} | head -14
+W=$(grep -o 'windows/launch=[0-9]*' $OUT/pmc_FETCH_SIZE.log | tail -1 | cut -d= -f2)
+python scripts/pmc_traffic.py /tmp/pmc/pmc_summary.json $OUT/pmc_traffic.json ${W:-} | head -14
 rm -rf /tmp/pmc_sq
-timeout -k 10 500 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d /tmp/pmc_sq/a -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-precision --seconds 60 > gpurun_out/pmc_sq.log 2>&1
+timeout -k 10 500 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d /tmp/pmc_sq/a -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-precision --seconds 60 > $OUT/pmc_sq.log 2>&1
 echo "sq a rc=$?"
-timeout -k 10 500 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d /tmp/pmc_sq/b -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-precision --seconds 60 >> gpurun_out/pmc_sq.log 2>&1
+timeout -k 10 500 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d /tmp/pmc_sq/b -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-precision --seconds 60 >> $OUT/pmc_sq.log 2>&1
 echo "sq b rc=$?"
 python scripts/pmc_summary.py /tmp/pmc_sq > /dev/null
-python scripts/sq_table.py /tmp/pmc_sq/pmc_summary.json > gpurun_out/sq_table.txt 2>&1; head -12 gpurun_out/sq_table.txt | cut -c1-200
+python scripts/sq_table.py /tmp/pmc_sq/pmc_summary.json > $OUT/sq_table.txt 2>&1; head -12 $OUT/sq_table.txt | cut -c1-200

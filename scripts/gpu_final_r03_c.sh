@@ -1,14 +1,15 @@
 #!/bin/bash
 # Round-3 evidence, call C: smoke, default bench line (precision + accuracy objects, PMC traffic from profiles/pmc_traffic.json), rocprof kernel stats
 set -u
+OUT="${OUT:-out}"
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-mkdir -p gpurun_out
+mkdir -p $OUT
 export TMPDIR=/tmp
-timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee gpurun_out/smoke.log
-timeout -k 10 600 python bench.py 2>gpurun_out/bench_default.err | tail -1 | tee gpurun_out/bench_default.log | cut -c1-300
+timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $OUT/smoke.log
+timeout -k 10 600 python bench.py --full 2>$OUT/bench_default.err | tail -1 | tee $OUT/bench_default.log | cut -c1-300
 rm -rf /tmp/prof
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-precision > gpurun_out/bench_prof.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-precision > $OUT/bench_prof.log 2>&1
 echo "prof rc=$?"
 f=$(find /tmp/prof -name "*kernel_stats.csv" | head -1)
-[ -n "$f" ] && cp "$f" gpurun_out/kernel_stats.csv
-python scripts/trace_summary.py "$(find /tmp/prof -name '*kernel_trace.csv' | head -1)" 60 > gpurun_out/trace_summary.txt; head -5 gpurun_out/trace_summary.txt | cut -c1-200
+[ -n "$f" ] && cp "$f" $OUT/kernel_stats.csv
+python scripts/trace_summary.py "$(find /tmp/prof -name '*kernel_trace.csv' | head -1)" 60 > $OUT/trace_summary.txt; head -5 $OUT/trace_summary.txt | cut -c1-200

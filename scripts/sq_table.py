@@ -5,7 +5,7 @@ import sys
 
 d = json.load(open(sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pmc_sq/pmc_summary.json"))
 tag = sys.argv[2] if len(sys.argv) > 2 else ""
-print(f"rocprofv3 --pmc (scripts/gpu_pmc_sq.sh, bench.py --steps 1 --seconds 60{', ' + tag if tag else ''}): MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs);")
+print(f"rocprofv3 --pmc (scripts/gpu_pmc_sq.sh, bench.py --full --steps 1 --seconds 60{', ' + tag if tag else ''}): MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs);")
 print("wave-time split = SQ_ACTIVE_INST_ANY, SQ_WAIT_INST_ANY, SQ_WAIT_ANY over SQ_WAVE_CYCLES; LDS = SQ_LDS_IDX_ACTIVE / (256 CUs x cycles) and the share of it that is SQ_LDS_BANK_CONFLICT")
 print("kernel (grid = workgroups) | launches | MFMA busy | wave time: issuing | issue-stalled | waiting (waitcnt, barrier) | LDS active / CU cycle | conflict share of LDS cycles")
 rows = []
