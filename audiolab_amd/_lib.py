@@ -20,6 +20,7 @@ F32, BF16, F16 = 0, 1, 2
 PROF_CONV3X3, PROF_CONV3X3_SMALL, PROF_TDF, PROF_PIX, PROF_POINTWISE, PROF_STFT, PROF_ISTFT = 1, 2, 3, 4, 5, 6, 7
 PROF_CONV3X3_REGW, PROF_CONV3X3_PIPE, PROF_CONV3X3_BIG, PROF_CONV3X3_BIG3 = 8, 9, 10, 11
 PROF_NN_GEMM, PROF_NN_CONV, PROF_NN_GEMM_H, PROF_NN_ATTN_H, PROF_NN_CONV_H, PROF_NN_DCONV_H, PROF_NN_NORM_H = 12, 13, 14, 15, 16, 17, 18
+PROF_NN_LSTM, PROF_NN_LOCALSTATE = 19, 20
 LAYOUT_REF, LAYOUT_NHWC = 0, 1
 ABI_VERSION = 1
 
@@ -175,6 +176,12 @@ _SIGNATURES = {
     "alsep_rfft_mag_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "alsep_dft_f64_workspace_bytes": (C.c_int64, [C.c_int64]),
     "alsep_dft_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64]),
+    "alsep_nn_lstm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "alsep_nn_localstate_softmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]),
+    "alsep_nn_blstm_unfold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int] * 5),
+    "alsep_nn_blstm_stitch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int] * 5),
+    "alsep_nn_group_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                      C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
 EXPORTS: Tuple[str, ...] = tuple(_SIGNATURES)

@@ -1660,3 +1660,5 @@ extern "C" int alsep_vr_band_spec(alsep_ctx* ctx, const float* spec_m, const flo
     ALSEP_LAUNCH_CHECK(ctx, "vr_band_spec_kernel");
     return ALSEP_OK;
 }
+
+#include "nn_hdemucs.h"

@@ -16,8 +16,9 @@ training-project tables (PARITY UNPINNED: upstream, uncited).
 
 Demucs.  ``htdemucs_6s.yaml`` (the orchestrator's multi-stem stage), ``htdemucs.yaml`` (one 4-source HTDemucs) and ``htdemucs_ft.yaml`` (a
 bag of four 4-source HTDemucs with demucs' per-source weights) load from the yaml and the ``.th`` packages it names; every member of a bag
-is read (a missing one is an error) and the members must agree on sources, samplerate and channels.  ``hdemucs_mmi.yaml`` (an HDemucs
-package) is not implemented.
+is read (a missing one is an error) and the members must agree on sources, samplerate and channels.  ``hdemucs_mmi.yaml`` is one HDemucs
+(Hybrid Demucs v3, hdemucs.py: BLSTM and LocalState on the GPU); a package's ``klass`` picks the network, for bag members too.  HDemucs
+runs in float32 only (``demucs_precision="f16"`` falls back with a WARNING).
 
 Multi-stem entries.  A roster value ``("multi", [(label, cfg), ...])`` describes an MDX-Net style file set that yields several stems: one
 network per label.
@@ -43,6 +44,7 @@ from . import _lib, wavio
 from ._lib import AlsepError, Context
 from .mdx import Predictor
 from .synth import synthetic_state_dict
+from .hdemucs import HDemucs, HDemucsConfig
 from .htdemucs import DemucsRunner, HTDemucs, HTDemucsConfig
 from .mdx23c import MDX23C, MDX23CConfig
 from .roformer import Roformer, RoformerConfig, RoformerRunner
@@ -117,7 +119,20 @@ MODEL_ROSTER: Dict[str, tuple] = {
     "htdemucs.yaml": ("demucs", HTDemucsConfig(sources=_DEMUCS4), {"shifts": 2, "overlap": 0.25}),
     "htdemucs_ft.yaml": ("demucs", HTDemucsConfig(sources=_DEMUCS4),
                          {"shifts": 2, "overlap": 0.25, "members": 4, "weights": [[1.0 if i == j else 0.0 for j in range(4)] for i in range(4)]}),
+    # the fourth Demucs name the reference downloads: one HDemucs (demucs 4 hdemucs.py, hdemucs_mmi's structure as recalled -- a real
+    # package's kwargs override it)
+    "hdemucs_mmi.yaml": ("demucs", HDemucsConfig(sources=_DEMUCS4), {"shifts": 2, "overlap": 0.25}),
 }
+def _demucs_config(path: str, pkg: dict):
+    """a demucs package's network configuration, by its class: HTDemucs or HDemucs (any other class is refused)"""
+    from . import th_reader
+    if pkg["klass"] == "HTDemucs":
+        return th_reader.htdemucs_config_from_kwargs(pkg["kwargs"])
+    if pkg["klass"] == "HDemucs":
+        return th_reader.hdemucs_config_from_kwargs(pkg["kwargs"])
+    raise AlsepError(f"{path}: a {pkg['klass']} package -- only HTDemucs and HDemucs are implemented")
+
+
 # BASELINE configs[1] "MDX-Net UVR 4-stem": four single-target networks of the in-tree geometry (mdxnet.py:247-251:
 # dim_f 3072, n_fft 6144) -- the bench workload; never reached by a file name of the reference
 _BENCH = _cfg(6144, 3072, 256)
@@ -329,7 +344,8 @@ class Separator:
         self.model_instance = inst
 
     def _load_demucs(self, model_filename: str, entry: tuple) -> None:
-        """("demucs", HTDemucsConfig, {shifts, overlap[, members, weights]}).  Weights, in this order: the files the reference has --
+        """("demucs", HTDemucsConfig or HDemucsConfig, {shifts, overlap[, members, weights]}); a package's klass picks the network.  Weights, in
+        this order: the files the reference has --
         ``<dir>/<name>.yaml`` (demucs' bag-of-models list, audiolab_amd.th_reader.resolve_demucs_bag) pointing at one
         ``<signature>-<checksum>.th`` per member (a pickled package: read by th_reader's allow-list unpickler, hyper-parameters from its
         ``kwargs``, ``state`` as the weights); ``<dir>/<name>.pt`` (a plain state_dict with demucs' parameter names; single models only);
@@ -351,9 +367,7 @@ class Separator:
             members = []
             for path in bag[0]:
                 pkg = th_reader.read_th(path)
-                if pkg["klass"] != "HTDemucs":
-                    raise AlsepError(f"{path}: a {pkg['klass']} package -- only HTDemucs is implemented")
-                members.append((th_reader.htdemucs_config_from_kwargs(pkg["kwargs"]), pkg["state"]))
+                members.append((_demucs_config(path, pkg), pkg["state"]))
             c0 = members[0][0]
             for path, (ci, _) in zip(bag[0][1:], members[1:]):
                 if (ci.sources, ci.samplerate, ci.audio_channels) != (c0.sources, c0.samplerate, c0.audio_channels):
@@ -363,9 +377,7 @@ class Separator:
             weights = "real"
         elif th_path is not None:
             pkg = th_reader.read_th(th_path)
-            if pkg["klass"] != "HTDemucs":
-                raise AlsepError(f"{th_path}: a {pkg['klass']} package -- only HTDemucs is implemented")
-            cfg = th_reader.htdemucs_config_from_kwargs(pkg["kwargs"])
+            cfg = _demucs_config(th_path, pkg)
             sd, weights = pkg["state"], "real"
         elif n_members == 1:
             sd = self._weights_file(model_filename) if not model_filename.endswith(".yaml") else None
@@ -376,7 +388,9 @@ class Separator:
             if not self.allow_synthetic:
                 raise AlsepError(f"model '{model_filename}': no weight file ({os.path.join(self.model_file_dir, model_filename)} naming a .th "
                                  f"package, or {pt}); random-init weights are only used with Separator(allow_synthetic=True)")
-            from .htdemucs import synthetic_state_dict as demucs_synth
+            from .hdemucs import synthetic_state_dict as hdemucs_synth
+            from .htdemucs import synthetic_state_dict as htdemucs_synth
+            demucs_synth = hdemucs_synth if isinstance(cfg, HDemucsConfig) else htdemucs_synth
             if n_members == 1:
                 seed = int.from_bytes(hashlib.sha256(model_filename.encode()).digest()[:4], "little")
                 sd, weights = demucs_synth(cfg, seed=seed), "synthetic"
@@ -389,17 +403,22 @@ class Separator:
         elif sd is not None:
             weights = "real"
         precision = self.demucs_precision
+        if precision == "f16" and any(isinstance(c, HDemucsConfig) for c, _ in (members or [(cfg, sd)])):
+            logger.warning("%s: an HDemucs -- the half-precision Demucs mode is an HTDemucs mode; running in float32", model_filename)
+            precision = "f32"
         if precision == "f16":
             bad = [c for c, _ in (members or [(cfg, sd)]) if c.bottom_channels % c.t_heads or c.bottom_channels // c.t_heads != 64]
             if bad:
                 logger.warning("%s: head size %d / %d is not 64 -- the half-precision Demucs mode needs 64; running in float32", model_filename,
                                bad[0].bottom_channels, bad[0].t_heads)
                 precision = "f32"
+        def make(c, sd_i):
+            return HDemucs(c, sd_i, ctx=self.ctx) if isinstance(c, HDemucsConfig) else HTDemucs(c, sd_i, ctx=self.ctx, precision=precision)
         if members is not None:
-            nets = [HTDemucs(c, sd_i, ctx=self.ctx, precision=precision) for c, sd_i in members]
+            nets = [make(c, sd_i) for c, sd_i in members]
             net, cfg = nets[0], nets[0].cfg
         else:
-            net = HTDemucs(cfg, sd, ctx=self.ctx, precision=precision)
+            net = make(cfg, sd)
             nets = net
         inst = _ModelInstance(model_filename, net, None, cfg.sources[0].capitalize(), None)
         inst.demucs = DemucsRunner(nets, shifts=int(opts.get("shifts", 2)), overlap=float(opts.get("overlap", 0.25)), sharded=self.sharded,

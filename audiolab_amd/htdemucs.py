@@ -28,6 +28,7 @@ per-pass finish.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
@@ -171,7 +172,83 @@ class _Conv:
             self.wh = wh.to(ctx.device)
 
 
-class HTDemucs:
+class _DemucsOps:
+    """the float32 building blocks shared by HTDemucs and HDemucs (hdemucs.py): thin wrappers over the C ABI on ``self.ctx``, with the
+    per-view caches ``_ws`` (statistics workspace) and ``_plans`` (STFT plans)"""
+
+    def _vec(self, t: torch.Tensor) -> torch.Tensor:
+        return t.detach().float().contiguous().to(self.ctx.device)
+
+    def _conv(self, x: torch.Tensor, H: int, W: int, cv: _Conv, stride=(1, 1), pad=(0, 0), dil=(1, 1), act=ACT_NONE,
+              out: Optional[torch.Tensor] = None, B: int = 1) -> Tuple[torch.Tensor, int, int]:
+        """x holds [B, H, W, cin] (possibly with zero rows beyond B*H*W); -> (y [B*Ho*Wo (+ spare), cout], Ho, Wo)"""
+        ctx = self.ctx
+        Ho = (H + 2 * pad[0] - dil[0] * (cv.kh - 1) - 1) // stride[0] + 1
+        Wo = (W + 2 * pad[1] - dil[1] * (cv.kw - 1) - 1) // stride[1] + 1
+        y = out if out is not None else ctx.empty((B * Ho * Wo, cv.cout))
+        ctx.check(ctx.lib.alsep_nn_conv2d(ctx.handle, _lib.ptr(x), _lib.ptr(cv.w), _lib.ptr(cv.scale), _lib.ptr(cv.shift), _lib.ptr(y), B,
+                                          H, W, cv.cin, cv.cout, cv.kh, cv.kw, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], act,
+                                          cv.cout, 0), "alsep_nn_conv2d")
+        return y, Ho, Wo
+
+    def _workspace(self, G: int, per_group: int) -> torch.Tensor:
+        need = int(self.ctx.lib.alsep_nn_stats_workspace_bytes(G, per_group))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = self.ctx.empty((max(need, 1 << 16),), torch.uint8)
+        return self._ws
+
+    def _norm(self, x: torch.Tensor, G: int, R: int, Cn: int, gamma, beta, act=ACT_NONE, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        ctx = self.ctx
+        co = Cn // 2 if act == ACT_GLU else Cn
+        y = out if out is not None else ctx.empty((G * R, co))
+        ctx.check(ctx.lib.alsep_nn_norm(ctx.handle, _lib.ptr(x), _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), G, R, Cn, 1e-5, act,
+                                        _lib.ptr(self._workspace(G, R * Cn))), "alsep_nn_norm")
+        return y
+
+    def _act(self, x: torch.Tensor, rows: int, Cn: int, act: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        ctx = self.ctx
+        y = out if out is not None else ctx.empty((rows, Cn // 2 if act == ACT_GLU else Cn))
+        ctx.check(ctx.lib.alsep_nn_act(ctx.handle, _lib.ptr(x), _lib.ptr(y), rows, Cn, act), "alsep_nn_act")
+        return y
+
+    def _scale_add(self, a: torch.Tensor, b: torch.Tensor, scale, rows: int, Cn: int) -> torch.Tensor:
+        ctx = self.ctx
+        y = ctx.empty((rows, Cn))
+        ctx.check(ctx.lib.alsep_nn_scale_add(ctx.handle, _lib.ptr(a), _lib.ptr(b), _lib.ptr(scale) if scale is not None else None,
+                                             _lib.ptr(y), rows, Cn), "alsep_nn_scale_add")
+        return y
+
+    def _meanstd(self, x: torch.Tensor, n: int) -> torch.Tensor:
+        ctx = self.ctx
+        stats = ctx.empty((2,))
+        ctx.check(ctx.lib.alsep_nn_meanstd(ctx.handle, _lib.ptr(x), 1, n, _lib.ptr(stats), _lib.ptr(self._workspace(1, n))), "alsep_nn_meanstd")
+        return stats
+
+    def _affine(self, x: torch.Tensor, stats: torch.Tensor, n: int, inverse: bool, eps: float = 1e-5) -> torch.Tensor:
+        ctx = self.ctx
+        y = torch.empty_like(x)
+        ctx.check(ctx.lib.alsep_nn_affine_stats(ctx.handle, _lib.ptr(x), _lib.ptr(y), _lib.ptr(stats), 1, n, eps, 1 if inverse else 0),
+                  "alsep_nn_affine_stats")
+        return y
+
+    def _plan(self, dim_t: int):
+        from .mdx import StftPlan
+        if dim_t not in self._plans:
+            self._plans[dim_t] = StftPlan(self.ctx, self.cfg.nfft, self.cfg.hop, self.cfg.nfft // 2, dim_t)
+        return self._plans[dim_t]
+
+    def _meanstd_b(self, x: torch.Tensor, B: int, n: int) -> torch.Tensor:
+        """per-sample (mean, unbiased std) of B samples of n values: one reduction per sample, so a sample's statistics do not depend on B"""
+        ctx = self.ctx
+        stats = ctx.empty((B, 2))
+        ws = self._workspace(1, n)
+        for b in range(B):
+            ctx.check(ctx.lib.alsep_nn_meanstd(ctx.handle, C.c_void_p(x.data_ptr() + 4 * b * n), 1, n, C.c_void_p(stats.data_ptr() + 8 * b),
+                                               _lib.ptr(ws)), "alsep_nn_meanstd")
+        return stats
+
+
+class HTDemucs(_DemucsOps):
     def __init__(self, cfg: HTDemucsConfig, state_dict: Dict[str, torch.Tensor], ctx: Optional[Context] = None, precision: str = "f32"):
         """``precision="f16"``: the half-precision mode (torch autocast restated): every convolution, Linear and
         attention product reads IEEE-half operands on the f16 matrix pipe and accumulates in float32; norms, statistics, the residual
@@ -227,10 +304,6 @@ class HTDemucs:
         v.precision = "f32"
         v._plans, v._pos, v._ws, v._ws_h = {}, {}, None, None
         return v
-
-    # -- parameters ---------------------------------------------------------------------------------------
-    def _vec(self, t: torch.Tensor) -> torch.Tensor:
-        return t.detach().float().contiguous().to(self.ctx.device)
 
     def _build(self, sd) -> None:
         cfg, ctx = self.cfg, self.ctx
@@ -303,59 +376,6 @@ class HTDemucs:
             return d
         self.layers = [tlayer(f"{p}.layers.{i}", i % 2 == 1) for i in range(cfg.t_layers)]
         self.layers_t = [tlayer(f"{p}.layers_t.{i}", i % 2 == 1) for i in range(cfg.t_layers)]
-
-    # -- thin wrappers over the C ABI -----------------------------------------------------------------------
-    def _conv(self, x: torch.Tensor, H: int, W: int, cv: _Conv, stride=(1, 1), pad=(0, 0), dil=(1, 1), act=ACT_NONE,
-              out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, int, int]:
-        """x holds [H, W, cin] (possibly with zero rows beyond H*W); -> (y [Ho*Wo (+ spare), cout], Ho, Wo)"""
-        ctx = self.ctx
-        Ho = (H + 2 * pad[0] - dil[0] * (cv.kh - 1) - 1) // stride[0] + 1
-        Wo = (W + 2 * pad[1] - dil[1] * (cv.kw - 1) - 1) // stride[1] + 1
-        y = out if out is not None else ctx.empty((Ho * Wo, cv.cout))
-        ctx.check(ctx.lib.alsep_nn_conv2d(ctx.handle, _lib.ptr(x), _lib.ptr(cv.w), _lib.ptr(cv.scale), _lib.ptr(cv.shift), _lib.ptr(y), 1,
-                                          H, W, cv.cin, cv.cout, cv.kh, cv.kw, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], act,
-                                          cv.cout, 0), "alsep_nn_conv2d")
-        return y, Ho, Wo
-
-    def _workspace(self, G: int, per_group: int) -> torch.Tensor:
-        need = int(self.ctx.lib.alsep_nn_stats_workspace_bytes(G, per_group))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = self.ctx.empty((max(need, 1 << 16),), torch.uint8)
-        return self._ws
-
-    def _norm(self, x: torch.Tensor, G: int, R: int, Cn: int, gamma, beta, act=ACT_NONE, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        ctx = self.ctx
-        co = Cn // 2 if act == ACT_GLU else Cn
-        y = out if out is not None else ctx.empty((G * R, co))
-        ctx.check(ctx.lib.alsep_nn_norm(ctx.handle, _lib.ptr(x), _lib.ptr(y), _lib.ptr(gamma), _lib.ptr(beta), G, R, Cn, 1e-5, act,
-                                        _lib.ptr(self._workspace(G, R * Cn))), "alsep_nn_norm")
-        return y
-
-    def _act(self, x: torch.Tensor, rows: int, Cn: int, act: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        ctx = self.ctx
-        y = out if out is not None else ctx.empty((rows, Cn // 2 if act == ACT_GLU else Cn))
-        ctx.check(ctx.lib.alsep_nn_act(ctx.handle, _lib.ptr(x), _lib.ptr(y), rows, Cn, act), "alsep_nn_act")
-        return y
-
-    def _scale_add(self, a: torch.Tensor, b: torch.Tensor, scale, rows: int, Cn: int) -> torch.Tensor:
-        ctx = self.ctx
-        y = ctx.empty((rows, Cn))
-        ctx.check(ctx.lib.alsep_nn_scale_add(ctx.handle, _lib.ptr(a), _lib.ptr(b), _lib.ptr(scale) if scale is not None else None,
-                                             _lib.ptr(y), rows, Cn), "alsep_nn_scale_add")
-        return y
-
-    def _meanstd(self, x: torch.Tensor, n: int) -> torch.Tensor:
-        ctx = self.ctx
-        stats = ctx.empty((2,))
-        ctx.check(ctx.lib.alsep_nn_meanstd(ctx.handle, _lib.ptr(x), 1, n, _lib.ptr(stats), _lib.ptr(self._workspace(1, n))), "alsep_nn_meanstd")
-        return stats
-
-    def _affine(self, x: torch.Tensor, stats: torch.Tensor, n: int, inverse: bool, eps: float = 1e-5) -> torch.Tensor:
-        ctx = self.ctx
-        y = torch.empty_like(x)
-        ctx.check(ctx.lib.alsep_nn_affine_stats(ctx.handle, _lib.ptr(x), _lib.ptr(y), _lib.ptr(stats), 1, n, eps, 1 if inverse else 0),
-                  "alsep_nn_affine_stats")
-        return y
 
     # -- layers ---------------------------------------------------------------------------------------------
     def _dconv(self, y: torch.Tensor, H: int, W: int, Cn: int, layers, freq: bool) -> torch.Tensor:
@@ -454,12 +474,6 @@ class HTDemucs:
             e1d = torch.cat([torch.cos(phase), torch.sin(phase)], dim=-1).contiguous()
             self._pos[key] = (e2d.to(self.ctx.device), e1d.to(self.ctx.device))
         return self._pos[key]
-
-    def _plan(self, dim_t: int):
-        from .mdx import StftPlan
-        if dim_t not in self._plans:
-            self._plans[dim_t] = StftPlan(self.ctx, self.cfg.nfft, self.cfg.hop, self.cfg.nfft // 2, dim_t)
-        return self._plans[dim_t]
 
     # -- forward --------------------------------------------------------------------------------------------
     def forward(self, mix: torch.Tensor) -> torch.Tensor:
@@ -652,16 +666,6 @@ class HTDemucs:
         x = self._scale_add(x, f, P["g2"], B * N, Cd)
         return self._norm_h(x, B, N, Cd, *P["norm_out"])
 
-    def _meanstd_b(self, x: torch.Tensor, B: int, n: int) -> torch.Tensor:
-        """per-sample (mean, unbiased std) of B samples of n values: one reduction per sample, so a sample's statistics do not depend on B"""
-        ctx = self.ctx
-        stats = ctx.empty((B, 2))
-        ws = self._workspace(1, n)
-        for b in range(B):
-            ctx.check(ctx.lib.alsep_nn_meanstd(ctx.handle, C.c_void_p(x.data_ptr() + 4 * b * n), 1, n, C.c_void_p(stats.data_ptr() + 8 * b),
-                                               _lib.ptr(ws)), "alsep_nn_meanstd")
-        return stats
-
     def _forward_h(self, mix: torch.Tensor) -> torch.Tensor:
         ctx, cfg = self.ctx, self.cfg
         lib, h = ctx.lib, ctx.handle
@@ -758,6 +762,9 @@ class HTDemucs:
 # units per batched forward of a half-precision network in DemucsRunner (ALSEP_DEMUCS_BATCH overrides).  Measured, htdemucs_6s 10 min
 # (profiles/demucs_half_batch_sweep.txt): batch 1 1.38 s, 2 0.97 s, 4 0.76 s, 8 0.70 s
 DEFAULT_F16_BATCH = 8
+# units of equal length per batched forward of a network that takes its chunks unpadded (HDemucs, ``pads_to_segment = False``) on the
+# float32 lanes: a batch lets the BLSTM recurrence see the frames of several units in one launch
+DEFAULT_UNPADDED_BATCH = 8
 
 
 def shift_offsets(shifts: int, max_shift: int, seed: int = 0) -> List[int]:
@@ -833,7 +840,11 @@ class DemucsRunner:
                 logging.getLogger(__name__).info("DemucsRunner: half-precision networks run on one lane (DESIGN section 6), not %d", int(lanes))
             lanes, graphs = 1, False
             self.batch = max(1, int(batch if batch is not None else os.environ.get("ALSEP_DEMUCS_BATCH", str(DEFAULT_F16_BATCH))))
-        self.batches_run = 0                                   # batched forwards of the last track (half-precision networks)
+        # networks that take their chunks as they are (HDemucs: demucs' apply_model pads a chunk to the training length only for a model
+        # with ``valid_length``): their units run ``unpadded_batch`` at a time (equal length, one member) through the batched forward
+        self.pads = [getattr(n, "pads_to_segment", True) for n in nets]
+        self.unpadded_batch = max(1, int(batch if batch is not None else DEFAULT_UNPADDED_BATCH))
+        self.batches_run = 0                                   # batched forwards of the last track (half-precision / unpadded networks)
         self._f32_rerun = False
         self._f32_nets: Dict[int, "HTDemucs"] = {}
         self.shifts, self.overlap, self.seed = shifts, overlap, seed
@@ -1051,6 +1062,23 @@ class DemucsRunner:
                     dst = C.c_void_p(accs[0][v].data_ptr() + 4 * (j0 * 2 * width + off))
                     ctx.check(lib.alsep_nn_vec_fma(h, dst, src, _lib.ptr(tri[seg]), n * 2, cl, width, seg), "alsep_nn_vec_fma")
 
+        def run_unpadded(lane_nets, lctx, lane_acc, batch_units):
+            """a network without training-length padding: up to ``unpadded_batch`` units of one member and one length as one batched forward
+            [B, 2, cl] on one lane (demucs' TensorChunk of the view, no padding), weighed from sample 0 of the output"""
+            v0, _, _, _, cl = batch_units[0]
+            vw0 = views[v0]
+            chunks = lctx.empty((len(batch_units), 2, cl))
+            for b, (v, offset, view_len, off, _) in enumerate(batch_units):
+                chunks[b] = root[:, offset + off: offset + off + cl]
+            yb = lane_nets[vw0.m].forward(chunks)                                     # [B, S, 2, cl]
+            self.batches_run += 1
+            for b, (v, offset, view_len, off, _) in enumerate(batch_units):
+                vw = views[v]
+                for s0, n, j0 in vw.runs:
+                    src = C.c_void_p(yb.data_ptr() + 4 * ((b * S + s0) * 2 * cl))
+                    dst = C.c_void_p(lane_acc[v].data_ptr() + 4 * (j0 * 2 * width + off))
+                    lctx.check(lctx.lib.alsep_nn_vec_fma(lctx.handle, dst, src, _lib.ptr(tri[vw.seg]), n * 2, cl, width, cl), "alsep_nn_vec_fma")
+
         if self.precision == "f16":
             self.batches_run = 0
             pending: List[tuple] = []
@@ -1061,14 +1089,28 @@ class DemucsRunner:
                 pending.append(unit)
             if pending:
                 run_batch(pending)
-        for i, unit in enumerate(units[lo:hi] if self.precision != "f16" else []):
+        # float32 work items: one unit of a padding network, or a batch of units of an unpadded one (same member, same length)
+        items: List[tuple] = []
+        for unit in units[lo:hi] if self.precision != "f16" else []:
+            m = views[unit[0]].m
+            prev = items[-1] if items else None
+            if self.pads[m]:
+                items.append((True, [unit]))
+            elif prev is not None and not prev[0] and len(prev[1]) < self.unpadded_batch and views[prev[1][0][0]].m == m and prev[1][0][4] == unit[4]:
+                prev[1].append(unit)
+            else:
+                items.append((False, [unit]))
+        if self.precision != "f16":
+            self.batches_run = 0
+        for i, (padded, item) in enumerate(items):
             k = i % len(lanes)
             lane_nets, st = lanes[k]
-            if st is None:
-                run_unit(k, lane_nets, st, accs[0], unit)
-            else:
-                with torch.cuda.stream(st):                      # torch's allocator ties the lane's temporaries to its stream
-                    run_unit(k, lane_nets, st, accs[k], unit)
+            acc_k = accs[0] if st is None else accs[k]
+            with torch.cuda.stream(st) if st is not None else contextlib.nullcontext():     # the lane's temporaries belong to its stream
+                if padded:
+                    run_unit(k, lane_nets, st, acc_k, item[0])
+                else:
+                    run_unpadded(lane_nets, lane_nets[0].ctx, acc_k, item)
         acc = accs[0]
         for k, (_, st) in enumerate(lanes):
             if st is None:

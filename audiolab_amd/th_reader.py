@@ -179,6 +179,52 @@ def htdemucs_config_from_kwargs(kwargs: dict):
     return dataclasses.replace(base, **over)
 
 
+# demucs.hdemucs.HDemucs.__init__'s own defaults (demucs 4.0.1, upstream; restated -- unpinned) for every option that is not a field of
+# HDemucsConfig
+_HDEMUCS_DEFAULTS = {
+    "channels_time": None, "wiener_iters": 0, "end_iters": 0, "wiener_residual": False, "cac": True, "rewrite": True, "hybrid": True,
+    "hybrid_old": False, "multi_freqs": None, "multi_freqs_depth": 2, "emb_smooth": True, "rescale": 0.1,
+}
+# structural options HDemucs must hold at these values here (MultiWrap, the non-hybrid and the old hybrid layouts, Wiener filtering, a
+# separate time-branch width and the magnitude / complex-as-channels switch are not implemented)
+_HDEMUCS_EXPECT = {"multi_freqs": None, "hybrid": True, "hybrid_old": False, "cac": True, "wiener_iters": 0, "channels_time": None,
+                   "rewrite": True}
+# construction / training-only options (initial scales, the embedding's initial smoothing, iterations of a disabled Wiener filter)
+_HDEMUCS_TRAINING_ONLY = {"rescale", "emb_smooth", "end_iters", "wiener_residual", "multi_freqs_depth", "dconv_init"}
+
+
+def hdemucs_config_from_kwargs(kwargs: dict):
+    """demucs.hdemucs.HDemucs(**kwargs) -> HDemucsConfig (the defaults are demucs' own).  A structural option this build does not implement
+    raises with its name, an unknown keyword raises too; training-only options are ignored."""
+    import dataclasses
+    from .hdemucs import HDemucsConfig, check_config
+    base = HDemucsConfig(segment_samples=40 * 44100)
+    fields = {f.name for f in dataclasses.fields(HDemucsConfig)}
+    over = {}
+    for k, v in kwargs.items():
+        if k == "sources":
+            over["sources"] = tuple(str(s) for s in v)
+        elif k == "segment":
+            sr = int(kwargs.get("samplerate", base.samplerate))
+            over["segment_samples"] = int(fractions.Fraction(v) * sr) if not isinstance(v, float) else int(v * sr)
+        elif k in ("nfreqs", "local_nfreqs"):
+            if v:
+                raise AlsepError(f"demucs package: HDemucs({k}={v!r}): LocalState frequency features are not implemented by this build")
+        elif k in fields and k not in _HDEMUCS_TRAINING_ONLY:
+            over[k] = type(getattr(base, k))(v)
+        elif k not in _HDEMUCS_DEFAULTS and k not in _HDEMUCS_TRAINING_ONLY:
+            raise AlsepError(f"demucs package: HDemucs({k}={v!r}) is not an option this build knows")
+    if "samplerate" in kwargs and "segment" not in kwargs:
+        over["segment_samples"] = 40 * int(kwargs["samplerate"])
+    for k, want in _HDEMUCS_EXPECT.items():
+        have = kwargs.get(k, _HDEMUCS_DEFAULTS[k])
+        if have != want and not (want is None and not have):
+            raise AlsepError(f"demucs package: HDemucs({k}={have!r}) is not implemented by this build (expects {want!r})")
+    cfg = dataclasses.replace(base, **over)
+    check_config(cfg)
+    return cfg
+
+
 def resolve_demucs_yaml(model_file_dir: str, yaml_name: str):
     """``<dir>/<name>.yaml`` of demucs' remote model zoo (``models: [signature, ...]``, optional ``weights``) -> the .th path of its one
     model; None when the yaml is absent.  Bags of several models (htdemucs_ft) are not implemented."""

@@ -79,7 +79,9 @@ enum {
     ALSEP_PROF_NN_ATTN_H = 15,   /* nn_attn_h_kernel (one-pass f16 attention) */
     ALSEP_PROF_NN_CONV_H = 16,   /* nn_conv_hh_kernel (f16 MFMA convolution) + its split-K reduction */
     ALSEP_PROF_NN_DCONV_H = 17,  /* nn_dconv_h_kernel (f16 MFMA convolution of HTDemucs' half-precision mode) */
-    ALSEP_PROF_NN_NORM_H = 18    /* nn_norm_h_* (GroupNorm / LayerNorm to half: statistics, final, apply) */
+    ALSEP_PROF_NN_NORM_H = 18,   /* nn_norm_h_* (GroupNorm / LayerNorm to half: statistics, final, apply) */
+    ALSEP_PROF_NN_LSTM = 19,     /* nn_lstm_kernel (the recurrence of HDemucs' BLSTM) */
+    ALSEP_PROF_NN_LOCALSTATE = 20 /* nn_localstate_softmax_kernel (HDemucs' LocalState bias / mask / softmax) */
 };
 int alsep_profile_begin(alsep_ctx* ctx, int category);
 int alsep_profile_end(alsep_ctx* ctx, double* total_ms, int64_t* launches);
@@ -322,6 +324,25 @@ int alsep_demucs_spec_out(alsep_ctx* ctx, const float* x, const float* stats, fl
                           int t_off, float scale);
 /* out [B,S,2,L] = (xt [B,L,S*2] * stdt + meant) + xs [B*S,2,L]   (the last lines of HTDemucs.forward) */
 int alsep_demucs_mix_out(alsep_ctx* ctx, const float* xt, const float* statst, const float* xs, float* out, int64_t B, int S, int64_t L);
+/* ---- HDemucs (csrc/nn_hdemucs.h) ----
+ * One bidirectional LSTM layer's recurrence (torch.nn.LSTM, gate order i, f, g, o), both directions and all N sequences in ONE launch:
+ *   pre [T, N, 8H] = x W_ih^T + b_ih + b_hh of the forward (columns 0 .. 4H) and the reverse direction (4H .. 8H);
+ *   whh_t [2, H, 4H] = W_hh^T of each direction (forward first);  h [T, N, 2H] = h_t, forward direction in the first H columns.
+ * Zero initial state.  16 <= H <= 512, H % 16 == 0. */
+int alsep_nn_lstm(alsep_ctx* ctx, const float* pre, const float* whh_t, float* h, int T, int N, int H);
+/* demucs LocalState between its two products, in place over scores [B*heads, T, ld] (rows: queries s, columns: keys t, already scaled):
+ * adds -sum_f (f+1) |t - s| / sqrt(nd) * sigmoid(qd[b, s, h*nd + f]) / 2, sets the diagonal to -100, softmax over t.
+ * qd: the query_decay projection, channels-last rows of qd_ld floats. */
+int alsep_nn_localstate_softmax(alsep_ctx* ctx, float* scores, const float* qd, int64_t B, int heads, int T, int ld, int nd, int64_t qd_ld);
+/* demucs BLSTM framing.  unfold: x [B, T, C] -> frames [width, B*nf, C], frames[w][b*nf + k] = x[b][k*stride + w] (zero beyond T).
+ * stitch: y [B, T, C] = skip + frames[t - k*stride][b*nf + k] with k = clamp((t - stride/2) / stride, 0, nf - 1); nf == 1: no framing. */
+int alsep_nn_blstm_unfold(alsep_ctx* ctx, const float* x, float* frames, int64_t B, int T, int C, int width, int stride, int nf);
+int alsep_nn_blstm_stitch(alsep_ctx* ctx, const float* frames, const float* skip, float* y, int64_t B, int T, int C, int width, int stride,
+                          int nf);
+/* nn.GroupNorm(G, C) over channels-last x [B, R, C], then act 0, 3 (GELU) or 4 (GLU); writes rows [r0, r0 + Ro) of each sample into
+ * y [B, Ro, C'] (the crop of HDecLayer after its norm2).  stats: 2 B G floats of device scratch. */
+int alsep_nn_group_norm(alsep_ctx* ctx, const float* x, float* y, const float* gamma, const float* beta, int64_t B, int R, int C, int G,
+                        float eps, int act, int r0, int Ro, float* stats);
 /* a bag of Demucs models, last step: V views (one shift pass of one member each) -> the stems out [S,2,L] in one pass,
  *   out[s,c,t] = stats[0] + stats[1] * sum_v coef[v*S+s] * q_v(row[v*S+s]*2 + c, t + cut[v]),
  *   q_v(r, x) = wsum[v][x] != 0 ? acc[v][r * ld[v] + x] / wsum[v][x] : 0;  row[v*S+s] < 0: view v does not carry source s.
