@@ -16,6 +16,7 @@
 //                        load, head gates in the epilogue, f16 out
 //   roformer_bandsplit_in_kernel   gather + RMSNorm of every band of a frame -> zero-padded f16 rows of one batched Linear
 //   nn_demucs_h.h        HTDemucs' half-precision mode: Demucs-geometry convolution, GroupNorm / LayerNorm to half, cross-attention
+//   vrnet_h.h            the VR networks' half-precision mode: convolution with folded BatchNorm and a fused decoder input, small kernels
 #include "alsep_common.h"
 #include <alsep_gfx950_asm.h>
 #include "nn_gemm_h2.h"
@@ -1007,4 +1008,5 @@ extern "C" int alsep_nn_attention_f16(alsep_ctx* ctx, const void* qkv, void* out
 #endif  // !ALSEP_NN_HALF_CONV_TU
 #ifndef ALSEP_NN_HALF_CONV_TU
 #include "nn_demucs_h.h"
+#include "vrnet_h.h"
 #endif

@@ -203,7 +203,7 @@ class Separator:
                  denoise: bool = False, max_batch: int = 32, sharded: bool = False, roster: Optional[Dict[str, tuple]] = None,
                  chunker: str = "margin", overlap: float = 0.25, compensate: Optional[float] = None,
                  allow_synthetic: bool = False, normalization_threshold: float = 0.9, f32_contraction: str = "split", nn_contraction: str = "exact",
-                 demucs_precision: str = "f32", **_ignored):
+                 demucs_precision: str = "f32", vr_precision: str = "f32", **_ignored):
         """``allow_synthetic=True`` (bench, tests): a roster name without a weight file gets seeded random-init weights.
         The default refuses to: a missing model file is an error, never plausible-looking noise."""
         self.log_level = log_level
@@ -243,6 +243,10 @@ class Separator:
         if demucs_precision not in ("f32", "f16"):
             raise AlsepError("demucs_precision must be 'f32' or 'f16'")
         self.demucs_precision = demucs_precision
+        # the VR networks' half-precision mode (vrnet.VRNet / VRNetNew(precision="f16")): opt-in under the same policy
+        if vr_precision not in ("f32", "f16"):
+            raise AlsepError("vr_precision must be 'f32' or 'f16'")
+        self.vr_precision = vr_precision
         self.model_instance: Optional[_ModelInstance] = None
         self._cache: Dict[str, _ModelInstance] = {}
 
@@ -538,7 +542,8 @@ class Separator:
         high_end_process}): a VR network behind the multi-band front / back end (vr_frontend.VRSeparator).  The runner options default
         to the values the reference's engine uses when AudioLab passes none (window 512, aggression 5, no TTA, no mirrored high end --
         audio-separator's ``vr_params`` defaults; upstream, uncited); the in-tree runner (vr.py:20-37: agg 10, mirroring) is
-        ``VRSeparator(net, params, agg=10, high_end_process=True)``.  float32 (the kernels of this family are fp32)."""
+        ``VRSeparator(net, params, agg=10, high_end_process=True)``.  The network runs in float32, or with ``Separator(vr_precision="f16")`` in
+        its half-precision mode (csrc/vrnet_h.h); the multi-band front / back end is float32 either way."""
         from .vr_frontend import MODEL_PARAMS, VRSeparator
         from . import vrnet
         spec, opts = entry[1], (entry[2] if len(entry) > 2 else {})
@@ -556,9 +561,9 @@ class Separator:
             weights = "synthetic"
             logger.warning("%s: no weight file under %s -- SYNTHETIC random-init weights (allow_synthetic=True)", model_filename, self.model_file_dir)
         if spec["arch"] == "new":
-            net = vrnet.VRNetNew(n_fft, sd, nout=spec["nout"], nout_lstm=spec["nout_lstm"], ctx=self.ctx)
+            net = vrnet.VRNetNew(n_fft, sd, nout=spec["nout"], nout_lstm=spec["nout_lstm"], ctx=self.ctx, precision=self.vr_precision)
         else:
-            net = vrnet.VRNet(n_fft, sd, variant=spec["arch"], ctx=self.ctx)
+            net = vrnet.VRNet(n_fft, sd, variant=spec["arch"], ctx=self.ctx, precision=self.vr_precision)
         labels = tuple(opts.get("labels", ("Instrumental", "Vocals")))
         inst = _ModelInstance(model_filename, net, None, labels[0], labels[1])
         inst.vr = VRSeparator(net, spec["params"], agg=int(opts.get("aggression", 5)), window_size=int(opts.get("window_size", 512)),

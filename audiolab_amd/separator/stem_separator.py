@@ -83,7 +83,7 @@ class EnsembleDemucsMDXMusicSeparationModel:
             invert_using_spec=True, use_autocast=not options.get("cpu", False) and options.get("precision", "fp16") != "fp32",
             dtype={"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32}.get(options.get("precision", "fp16")),
             chunker=options.get("chunker", "ola"), overlap=float(options.get("overlap", 0.25)), normalization_threshold=0.9,
-            sharded=num_gpus > 1)
+            sharded=num_gpus > 1, vr_precision=options.get("vr_precision", "f32"))
         self.ctx = self.separator.ctx
         self.vocals_only = bool(options.get("vocals_only", False))
         self.separate_drums = bool(options.get("separate_drums", False))
@@ -486,5 +486,6 @@ def separate_music(input_dict: Dict[str, List[str]], callback: Callable = None, 
         "chunker": kwargs.get("chunker", "ola"),
         "overlap": kwargs.get("overlap", 0.25),
         "num_gpus": kwargs.get("num_gpus", 1),
+        "vr_precision": kwargs.get("vr_precision", "f32"),       # engine option only (wrappers/separate.py engine_options)
     }
     return predict_with_model(options, callback, separator=kwargs.get("separator"))

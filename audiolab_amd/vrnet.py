@@ -11,10 +11,17 @@ models (spec_utils.py, librosa resampling) is not built, so the network is reach
 
 Tensors are channels-last on the device: ``[B, bins, frames, C]``; the reference layout ``[B, C, bins, frames]`` exists
 at the ``forward`` / ``predict`` boundary.
+
+``precision="f16"`` (opt-in; the reference runs these networks with ``model.half()``, vr.py:35-36) runs the half-precision kernels of
+csrc/vrnet_h.h: weights and the activations between layers are IEEE half, products on the f16 matrix pipe with float32 accumulation,
+BatchNorm as a float32 scale / shift in the convolution's epilogue, and the decoders read their upsampled input and their skip straight
+from the two sources (no resize / copy launch, no concatenated tensor).  The input is rounded once on entry; the last convolution, the
+mask and -- in ``VRNetNew`` -- the LSTM module stay float32.
 """
 from __future__ import annotations
 
 import ctypes as C
+import logging
 from typing import Dict, Optional, Sequence, Tuple
 
 import torch
@@ -26,6 +33,8 @@ from ._lib import AlsepError, Context
 WIDTHS = {"nets": (16, 8, 16, 16, 32), "nets_61968KB": (32, 16, 32, 32, 64), "nets_123821KB": (32, 16, 32, 32, 64),
           "nets_123812KB": (32, 16, 32, 32, 64)}
 ACT = {"none": 0, "relu": 1, "leaky": 2}
+PRECISIONS = ("f32", "f16")
+logger = logging.getLogger(__name__)
 
 
 def base_aspp_param_shapes(prefix: str, nin: int, ch: int):
@@ -91,12 +100,28 @@ def random_state_dict(widths: Sequence[int], seed: int = 0) -> Dict[str, torch.T
 
 
 class _Conv:
-    """Conv2d(bias=False) [+ BatchNorm2d eval] with weights packed [KH][KW][Cin][Cout] on the device."""
+    """Conv2d(bias=False) [+ BatchNorm2d eval] with weights packed [KH][KW][Cin][Cout] on the device; ``precision="f16"``: IEEE half
+    [Cout][Kp], k = (dy, dx, ci) zero-padded to a multiple of 32.  BatchNorm is a float32 scale / shift in either precision."""
 
-    def __init__(self, ctx: Context, sd, conv_key: str, bn_prefix: Optional[str], act: str, stride=1, pad=0, dil=1, eps=1e-5):
+    def __init__(self, ctx: Context, sd, conv_key: str, bn_prefix: Optional[str], act: str, stride=1, pad=0, dil=1, eps=1e-5,
+                 precision: str = "f32", zero_in: Tuple[int, int] = (0, 0)):
+        """``zero_in = (at, n)`` (f16): n input channels of zero weights inserted at channel ``at`` -- the layer then reads an input whose
+        channel count is a multiple of 8 (16-byte staging) and ignores the inserted channels."""
         w = sd[conv_key].float()
+        self.name = conv_key[:-len(".weight")]
+        self.zero_in = tuple(zero_in)
+        if self.zero_in[1]:
+            at, n = self.zero_in
+            w = torch.cat([w[:, :at], torch.zeros((w.shape[0], n) + tuple(w.shape[2:])), w[:, at:]], dim=1)
         self.cout, self.cin, self.kh, self.kw = w.shape
-        self.w = w.permute(2, 3, 1, 0).contiguous().to(ctx.device)
+        if precision == "f16":
+            k = self.kh * self.kw * self.cin
+            self.kp = -(-k // 32) * 32
+            wp = torch.zeros((self.cout, self.kp), dtype=torch.float16)
+            wp[:, :k] = w.permute(0, 2, 3, 1).reshape(self.cout, k).half()
+            self.w = wp.to(ctx.device)
+        else:
+            self.w = w.permute(2, 3, 1, 0).contiguous().to(ctx.device)
         if bn_prefix is not None:
             gamma, beta = sd[bn_prefix + ".weight"].float(), sd[bn_prefix + ".bias"].float()
             mean, var = sd[bn_prefix + ".running_mean"].float(), sd[bn_prefix + ".running_var"].float()
@@ -116,8 +141,11 @@ class _Conv:
 class VRNet:
     """``CascadedASPPNet(n_fft)`` of the reference; ``variant`` picks the channel widths of one of its files."""
 
-    def __init__(self, n_fft: int, state_dict: Dict[str, torch.Tensor], variant: str = "nets_61968KB", ctx: Optional[Context] = None):
+    def __init__(self, n_fft: int, state_dict: Dict[str, torch.Tensor], variant: str = "nets_61968KB", ctx: Optional[Context] = None,
+                 precision: str = "f32", trace=None):
         self.ctx = ctx if ctx is not None else _lib.default_context(None)
+        self._set_precision(precision, trace)
+        self._twin_make = lambda: VRNet(n_fft, state_dict, variant=variant, ctx=self.ctx)
         if variant not in WIDTHS:
             raise AlsepError(f"unknown VR net variant '{variant}' (have {sorted(WIDTHS)})")
         self.widths = WIDTHS[variant]
@@ -132,37 +160,76 @@ class VRNet:
         w1, b2, w2, b3, w3 = self.widths
         self.nets = {p: self._build_base(sd, p, nin, ch) for p, nin, ch in (
             ("stg1_low_band_net", 2, w1), ("stg1_high_band_net", 2, w1), ("stg2_full_band_net", b2, w2), ("stg3_full_band_net", b3, w3))}
-        self.stg2_bridge = _Conv(self.ctx, sd, "stg2_bridge.conv.0.weight", "stg2_bridge.conv.1", "relu")
-        self.stg3_bridge = _Conv(self.ctx, sd, "stg3_bridge.conv.0.weight", "stg3_bridge.conv.1", "relu")
-        self.out = _Conv(self.ctx, sd, "out.weight", None, "none")
+        self.stg2_bridge = self._mk(sd, "stg2_bridge.conv.0.weight", "stg2_bridge.conv.1", "relu")
+        self.stg3_bridge = self._mk(sd, "stg3_bridge.conv.0.weight", "stg3_bridge.conv.1", "relu")
+        self.out = self._mk(sd, "out.weight", None, "none")
 
     # -- construction ------------------------------------------------------------------------------
+    def _set_precision(self, precision: str, trace) -> None:
+        if precision not in PRECISIONS:
+            raise AlsepError(f"VR net precision must be one of {PRECISIONS}, got '{precision}'")
+        self.precision, self.half = precision, precision == "f16"
+        self.adt = torch.float16 if self.half else torch.float32        # the type of the activations between layers
+        self.trace = trace                  # f16: trace(name, kind, inputs, output) per layer call (tests); no effect when None
+        self.fuse_decoder = True            # f16: False runs resize + copy + conv (the cross-check of the fused decoder input)
+        self.layers = []                    # f16: the names a forward passes to ``trace``
+        self._logits_finite = None          # f16: a device flag of the last forward (vr_inference's non-finite guard)
+        self._twin = None
+
+    def _mk(self, sd, conv_key, bn_prefix, act, stride=1, pad=0, dil=1, zero_in=(0, 0)) -> _Conv:
+        L = _Conv(self.ctx, sd, conv_key, bn_prefix, act, stride, pad, dil, precision=self.precision, zero_in=zero_in)
+        self.layers.append(L.name)
+        return L
+
+    def float32_twin(self):
+        """The same weights in float32 (built on first use): what ``vr_inference`` re-runs a batch on when the half network's output is
+        not finite."""
+        if not self.half:
+            return self
+        if self._twin is None:
+            self._twin = self._twin_make()
+            self._twin.offset = self.offset
+        return self._twin
+
+    def _note(self, name, kind, inputs, out) -> None:
+        if self.trace is not None:
+            self.trace(name, kind, inputs, out)
+
     def _build_base(self, sd, p, nin, ch):
         c = self.ctx
-        net = {"ch": ch}
+        net = {"ch": ch, "name": p}
         for i in (1, 2, 3, 4):                                # Encoder: LeakyReLU, conv2 has stride 2 (nets*.py:12-15)
-            net[f"enc{i}.conv1"] = _Conv(c, sd, f"{p}.enc{i}.conv1.conv.0.weight", f"{p}.enc{i}.conv1.conv.1", "leaky", 1, 1)
-            net[f"enc{i}.conv2"] = _Conv(c, sd, f"{p}.enc{i}.conv2.conv.0.weight", f"{p}.enc{i}.conv2.conv.1", "leaky", 2, 1)
-        net["aspp.conv1"] = _Conv(c, sd, f"{p}.aspp.conv1.1.conv.0.weight", f"{p}.aspp.conv1.1.conv.1", "relu")
-        net["aspp.conv2"] = _Conv(c, sd, f"{p}.aspp.conv2.conv.0.weight", f"{p}.aspp.conv2.conv.1", "relu")
+            net[f"enc{i}.conv1"] = self._mk(sd, f"{p}.enc{i}.conv1.conv.0.weight", f"{p}.enc{i}.conv1.conv.1", "leaky", 1, 1)
+            net[f"enc{i}.conv2"] = self._mk(sd, f"{p}.enc{i}.conv2.conv.0.weight", f"{p}.enc{i}.conv2.conv.1", "leaky", 2, 1)
+        net["aspp.conv1"] = self._mk(sd, f"{p}.aspp.conv1.1.conv.0.weight", f"{p}.aspp.conv1.1.conv.1", "relu")
+        net["aspp.conv2"] = self._mk(sd, f"{p}.aspp.conv2.conv.0.weight", f"{p}.aspp.conv2.conv.1", "relu")
         for j, d in zip((3, 4, 5), (4, 8, 16)):              # separable: depthwise 3x3 dilated, pointwise + BN + ReLU
             dw = sd[f"{p}.aspp.conv{j}.conv.0.weight"].float()
-            net[f"aspp.conv{j}.dw"] = (dw.reshape(dw.shape[0], 3, 3).contiguous().to(c.device), d)
-            net[f"aspp.conv{j}.pw"] = _Conv(c, sd, f"{p}.aspp.conv{j}.conv.1.weight", f"{p}.aspp.conv{j}.conv.2", "relu")
-        net["aspp.bottleneck"] = _Conv(c, sd, f"{p}.aspp.bottleneck.0.conv.0.weight", f"{p}.aspp.bottleneck.0.conv.1", "relu")
+            net[f"aspp.conv{j}.dw"] = (dw.reshape(dw.shape[0], 3, 3).contiguous().to(self.adt).to(c.device), d)
+            self.layers.append(f"{p}.aspp.conv{j}.conv.0")
+            net[f"aspp.conv{j}.pw"] = self._mk(sd, f"{p}.aspp.conv{j}.conv.1.weight", f"{p}.aspp.conv{j}.conv.2", "relu")
+        net["aspp.bottleneck"] = self._mk(sd, f"{p}.aspp.bottleneck.0.conv.0.weight", f"{p}.aspp.bottleneck.0.conv.1", "relu")
+        self.layers += [f"{p}.aspp.pool", f"{p}.aspp.resize"]
         for i in (4, 3, 2, 1):
-            net[f"dec{i}"] = _Conv(c, sd, f"{p}.dec{i}.conv.conv.0.weight", f"{p}.dec{i}.conv.conv.1", "relu", 1, 1)
+            net[f"dec{i}"] = self._mk(sd, f"{p}.dec{i}.conv.conv.0.weight", f"{p}.dec{i}.conv.conv.1", "relu", 1, 1)
         return net
 
     # -- kernels -------------------------------------------------------------------------------------
-    def _conv(self, L: _Conv, x: torch.Tensor, y: Optional[torch.Tensor] = None, c0: int = 0) -> torch.Tensor:
+    def _conv(self, L: _Conv, x: torch.Tensor, y: Optional[torch.Tensor] = None, c0: int = 0, out_f32: bool = False) -> torch.Tensor:
+        """``out_f32`` (f16 only): a float32 result -- the logits of the mask and the LSTM module's input."""
         b, h, w, cin = x.shape
         if cin != L.cin:
             raise AlsepError(f"conv expects {L.cin} input channels, got {cin}")
         ho, wo = L.out_hw(h, w)
         if y is None:
-            y = self.ctx.empty((b, ho, wo, L.cout))
+            y = self.ctx.empty((b, ho, wo, L.cout), torch.float32 if out_f32 else self.adt)
         ctx = self.ctx
+        if self.half:
+            ctx.check(ctx.lib.alsep_vr_conv_h(ctx.handle, _lib.ptr(x), _lib.ptr(L.w), _lib.ptr(L.scale), _lib.ptr(L.shift), _lib.ptr(y),
+                                              int(y.dtype == torch.float16), b, h, w, L.cin, L.cout, L.kp, L.kh, L.kw, L.stride, L.pad[0],
+                                              L.pad[1], L.dil[0], L.dil[1], L.act, y.shape[3], c0), "alsep_vr_conv_h")
+            self._note(L.name, "conv", (x,), y[..., c0:c0 + L.cout])
+            return y
         ctx.check(ctx.lib.alsep_vr_conv2d(ctx.handle, _lib.ptr(x), _lib.ptr(L.w), _lib.ptr(L.scale), _lib.ptr(L.shift), _lib.ptr(y),
                                           b, h, w, L.cin, L.cout, L.kh, L.kw, L.stride, L.pad[0], L.pad[1], L.dil[0], L.dil[1], L.act,
                                           y.shape[3], c0),
@@ -172,12 +239,20 @@ class VRNet:
     def _resize(self, x, ho, wo, y, c0):
         b, h, w, c = x.shape
         ctx = self.ctx
+        if self.half:
+            ctx.check(ctx.lib.alsep_vr_resize_bilinear_h(ctx.handle, _lib.ptr(x), _lib.ptr(y), b, h, w, c, ho, wo, y.shape[3], c0),
+                      "alsep_vr_resize_bilinear_h")
+            return
         ctx.check(ctx.lib.alsep_vr_resize_bilinear(ctx.handle, _lib.ptr(x), _lib.ptr(y), b, h, w, c, ho, wo, y.shape[3], c0),
                   "alsep_vr_resize_bilinear")
 
     def _copy(self, x, y, c0, w_off=0):
         b, h, wx, c = x.shape
         ctx = self.ctx
+        if self.half:
+            ctx.check(ctx.lib.alsep_vr_copy_slice_h(ctx.handle, _lib.ptr(x), _lib.ptr(y), b * h, wx, c, w_off, y.shape[2], y.shape[3], c0),
+                      "alsep_vr_copy_slice_h")
+            return
         ctx.check(ctx.lib.alsep_vr_copy_slice(ctx.handle, _lib.ptr(x), _lib.ptr(y), b * h, wx, c, w_off, y.shape[2], y.shape[3], c0),
                   "alsep_vr_copy_slice")
 
@@ -188,25 +263,61 @@ class VRNet:
         ho, wo = 2 * h, 2 * w
         if skip.shape[1] != ho or skip.shape[2] < wo:
             raise AlsepError(f"decoder: skip {tuple(skip.shape)} does not fit the upsampled {ho}x{wo} map")
-        cat = self.ctx.empty((b, ho, wo, c + skip.shape[3]))
+        w_off = (skip.shape[2] - wo) // 2
+        if self.half and self.fuse_decoder:
+            # the convolution reads both sources itself: no resize / copy launch, no concatenated tensor
+            if c + skip.shape[3] != L.cin or L.stride != 1 or L.dil != (1, 1) or L.pad[0] != L.pad[1]:
+                raise AlsepError(f"decoder: {c} + {skip.shape[3]} channels into a convolution of {L.cin}")
+            ctx = self.ctx
+            y = ctx.empty((b, ho + 2 * L.pad[0] - L.kh + 1, wo + 2 * L.pad[1] - L.kw + 1, L.cout), self.adt)
+            ctx.check(ctx.lib.alsep_vr_decoder_conv_h(ctx.handle, _lib.ptr(x), _lib.ptr(skip), _lib.ptr(L.w), _lib.ptr(L.scale), _lib.ptr(L.shift),
+                                                      _lib.ptr(y), 1, b, h, w, c, skip.shape[2], skip.shape[3], w_off, L.cout, L.kp, L.kh, L.kw,
+                                                      L.pad[0], L.act, L.cout, 0), "alsep_vr_decoder_conv_h")
+            self._note(L.name, "decoder", (x[..., :L.zero_in[0]] if L.zero_in[1] else x, skip), y)
+            return y
+        cat = self.ctx.empty((b, ho, wo, c + skip.shape[3]), self.adt)
         self._resize(x, ho, wo, cat, 0)
-        self._copy(skip, cat, c, (skip.shape[2] - wo) // 2)
+        self._copy(skip, cat, c, w_off)
+        if self.half:                                          # the unfused cross-check: traced as the same layer
+            trace, self.trace = self.trace, None
+            y = self._conv(L, cat)
+            self.trace = trace
+            self._note(L.name, "decoder", (x[..., :L.zero_in[0]] if L.zero_in[1] else x, skip), y)
+            return y
         return self._conv(L, cat)
+
+    def _pooled_branch(self, net, x, cat):
+        """ASPP conv1: mean over bins, 1x1 conv, resized back into channels [0, c) of ``cat``."""
+        ctx = self.ctx
+        b, h, w, c = x.shape
+        pooled = ctx.empty((b, 1, w, c), self.adt)
+        if self.half:
+            ctx.check(ctx.lib.alsep_vr_mean_hh(ctx.handle, _lib.ptr(x), _lib.ptr(pooled), b, h, w, c), "alsep_vr_mean_hh")
+            self._note(net["name"] + ".aspp.pool", "mean", (x,), pooled)
+        else:
+            ctx.check(ctx.lib.alsep_vr_mean_h(ctx.handle, _lib.ptr(x), _lib.ptr(pooled), b, h, w, c), "alsep_vr_mean_h")
+        t = self._conv(net["aspp.conv1"], pooled)
+        self._resize(t, h, w, cat, 0)
+        if self.half:
+            self._note(net["name"] + ".aspp.resize", "resize", (t,), cat[..., :c])
 
     def _aspp(self, net, x):
         """layers*.py:96-125."""
         ctx = self.ctx
         b, h, w, c = x.shape
-        cat = ctx.empty((b, h, w, 5 * c))
-        pooled = ctx.empty((b, 1, w, c))
-        ctx.check(ctx.lib.alsep_vr_mean_h(ctx.handle, _lib.ptr(x), _lib.ptr(pooled), b, h, w, c), "alsep_vr_mean_h")
-        self._resize(self._conv(net["aspp.conv1"], pooled), h, w, cat, 0)
+        cat = ctx.empty((b, h, w, 5 * c), self.adt)
+        self._pooled_branch(net, x, cat)
         self._conv(net["aspp.conv2"], x, cat, c)
         for k, j in enumerate((3, 4, 5)):
             dw, d = net[f"aspp.conv{j}.dw"]
-            t = ctx.empty((b, h, w, c))
-            ctx.check(ctx.lib.alsep_vr_depthwise(ctx.handle, _lib.ptr(x), _lib.ptr(dw), _lib.ptr(t), b, h, w, c, 3, 3, d, d),
-                      "alsep_vr_depthwise")
+            t = ctx.empty((b, h, w, c), self.adt)
+            if self.half:
+                ctx.check(ctx.lib.alsep_vr_depthwise_h(ctx.handle, _lib.ptr(x), _lib.ptr(dw), _lib.ptr(t), b, h, w, c, 3, 3, d, d),
+                          "alsep_vr_depthwise_h")
+                self._note(f"{net['name']}.aspp.conv{j}.conv.0", "depthwise", (x, dw, d), t)
+            else:
+                ctx.check(ctx.lib.alsep_vr_depthwise(ctx.handle, _lib.ptr(x), _lib.ptr(dw), _lib.ptr(t), b, h, w, c, 3, 3, d, d),
+                          "alsep_vr_depthwise")
             self._conv(net[f"aspp.conv{j}.pw"], t, cat, (2 + k) * c)
         return self._conv(net["aspp.bottleneck"], cat)
 
@@ -232,22 +343,23 @@ class VRNet:
             raise AlsepError(f"VRNet input must be float32 [B, >= {self.output_bin} bins, frames, 2], got {tuple(x.shape)}")
         x = x.contiguous()
         mix = x[:, : self.output_bin].contiguous()
-        xin = x[:, : self.max_bin].contiguous()
+        xin = x[:, : self.max_bin].to(self.adt).contiguous()     # f16: the one rounding of the input
         b, hh, w, _ = xin.shape
         bandw = hh // 2
         w1, b2, w2, b3, w3 = self.widths
         low = self._base("stg1_low_band_net", xin[:, :bandw].contiguous())
         high = self._base("stg1_high_band_net", xin[:, bandw:].contiguous())
-        h1 = ctx.empty((b, hh, w, 2 + w1))                      # cat([x, aux1], channels)
+        h1 = ctx.empty((b, hh, w, 2 + w1), self.adt)            # cat([x, aux1], channels)
         self._copy(xin, h1, 0)
         aux1 = torch.cat([low, high], dim=1).contiguous()       # along bins: plain tensor plumbing
         self._copy(aux1, h1, 2)
         aux2 = self._base("stg2_full_band_net", self._conv(self.stg2_bridge, h1))
-        h2 = ctx.empty((b, hh, w, 2 + w1 + w2))
+        h2 = ctx.empty((b, hh, w, 2 + w1 + w2), self.adt)
         self._copy(h1, h2, 0)
         self._copy(aux2, h2, 2 + w1)
         h3 = self._base("stg3_full_band_net", self._conv(self.stg3_bridge, h2))
-        logit = self._conv(self.out, h3)
+        logit = self._conv(self.out, h3, out_f32=True)
+        self._logits_finite = torch.isfinite(logit).all() if self.half else None
         out = ctx.empty(tuple(mix.shape))
         split, aggr = (int(aggressiveness["split_bin"]), float(aggressiveness["value"])) if aggressiveness else (0, -1.0)
         ctx.check(ctx.lib.alsep_vr_mask(ctx.handle, _lib.ptr(logit), _lib.ptr(mix), _lib.ptr(out), b, logit.shape[1], self.output_bin,
@@ -307,6 +419,12 @@ def vr_inference(net: VRNet, x_spec: torch.Tensor, aggressiveness: Optional[dict
             if win.shape[2] != window_size:
                 raise AlsepError("vr_inference: window runs past the padded spectrogram")
             out = net.forward_nhwc(win, aggressiveness)                            # [nb, output_bin, window, 2]
+            if getattr(net, "half", False) and not (bool(net._logits_finite) and bool(torch.isfinite(out).all())):
+                # a half activation can overflow where float32 does not (the logits are looked at too: the sigmoid of an infinite logit
+                # is finite): this batch of windows again on the float32 kernels
+                logger.warning("vr_inference: the half-precision network's result for windows %d..%d is not finite -- running them in "
+                               "float32", w0, w0 + nb - 1)
+                out = net.float32_twin().forward_nhwc(win, aggressiveness)
             out = out[:, :, off:window_size - off] if off > 0 else out
             preds.extend(out[i] for i in range(nb))
         return torch.cat(preds, dim=1).permute(2, 0, 1)                            # [2, bins, n_window * roi]
@@ -392,8 +510,10 @@ class VRNetNew(VRNet):
     """``CascadedNet(n_fft, nout, nout_lstm)`` of nets_new.py; parameter names as in the reference module."""
 
     def __init__(self, n_fft: int, state_dict: Dict[str, torch.Tensor], nout: int = 32, nout_lstm: int = 128,
-                 ctx: Optional[Context] = None):
+                 ctx: Optional[Context] = None, precision: str = "f32", trace=None):
         self.ctx = ctx if ctx is not None else _lib.default_context(None)
+        self._set_precision(precision, trace)
+        self._twin_make = lambda: VRNetNew(n_fft, state_dict, nout=nout, nout_lstm=nout_lstm, ctx=self.ctx)
         shapes = cascaded_new_param_shapes(n_fft, nout, nout_lstm)
         for n, shape in shapes:
             if n not in state_dict:
@@ -405,25 +525,31 @@ class VRNetNew(VRNet):
         sd = state_dict
         self.base = {p: self._build_basenet(sd, p) for p in ("stg1_low_band_net.0", "stg1_high_band_net", "stg2_low_band_net.0",
                                                              "stg2_high_band_net", "stg3_full_band_net")}
-        self.stg1_low_tail = _Conv(self.ctx, sd, "stg1_low_band_net.1.conv.0.weight", "stg1_low_band_net.1.conv.1", "relu")
-        self.stg2_low_tail = _Conv(self.ctx, sd, "stg2_low_band_net.1.conv.0.weight", "stg2_low_band_net.1.conv.1", "relu")
-        self.out = _Conv(self.ctx, sd, "out.weight", None, "none")
+        self.stg1_low_tail = self._mk(sd, "stg1_low_band_net.1.conv.0.weight", "stg1_low_band_net.1.conv.1", "relu")
+        self.stg2_low_tail = self._mk(sd, "stg2_low_band_net.1.conv.0.weight", "stg2_low_band_net.1.conv.1", "relu")
+        self.out = self._mk(sd, "out.weight", None, "none")
 
     def _build_basenet(self, sd, p):
         c = self.ctx
-        net = {"enc1": _Conv(c, sd, f"{p}.enc1.conv.0.weight", f"{p}.enc1.conv.1", "relu", 1, 1)}
+        net = {"name": p, "enc1": self._mk(sd, f"{p}.enc1.conv.0.weight", f"{p}.enc1.conv.1", "relu", 1, 1)}
+        self.layers += [f"{p}.aspp.pool", f"{p}.aspp.resize", f"{p}.lstm_dec2.lstm"]
         for i in (2, 3, 4, 5):                                # Encoder (layers_new.py:30-40): conv1 strided, LeakyReLU
-            net[f"enc{i}.conv1"] = _Conv(c, sd, f"{p}.enc{i}.conv1.conv.0.weight", f"{p}.enc{i}.conv1.conv.1", "leaky", 2, 1)
-            net[f"enc{i}.conv2"] = _Conv(c, sd, f"{p}.enc{i}.conv2.conv.0.weight", f"{p}.enc{i}.conv2.conv.1", "leaky", 1, 1)
-        net["aspp.conv1"] = _Conv(c, sd, f"{p}.aspp.conv1.1.conv.0.weight", f"{p}.aspp.conv1.1.conv.1", "relu")
-        net["aspp.conv2"] = _Conv(c, sd, f"{p}.aspp.conv2.conv.0.weight", f"{p}.aspp.conv2.conv.1", "relu")
+            net[f"enc{i}.conv1"] = self._mk(sd, f"{p}.enc{i}.conv1.conv.0.weight", f"{p}.enc{i}.conv1.conv.1", "leaky", 2, 1)
+            net[f"enc{i}.conv2"] = self._mk(sd, f"{p}.enc{i}.conv2.conv.0.weight", f"{p}.enc{i}.conv2.conv.1", "leaky", 1, 1)
+        net["aspp.conv1"] = self._mk(sd, f"{p}.aspp.conv1.1.conv.0.weight", f"{p}.aspp.conv1.1.conv.1", "relu")
+        net["aspp.conv2"] = self._mk(sd, f"{p}.aspp.conv2.conv.0.weight", f"{p}.aspp.conv2.conv.1", "relu")
         for j, d in zip((3, 4, 5), ((4, 2), (8, 4), (12, 6))):           # nets_new.py:11, layers_new.py:83-91
-            net[f"aspp.conv{j}"] = _Conv(c, sd, f"{p}.aspp.conv{j}.conv.0.weight", f"{p}.aspp.conv{j}.conv.1", "relu", 1, d, d)
-        net["aspp.bottleneck"] = _Conv(c, sd, f"{p}.aspp.bottleneck.conv.0.weight", f"{p}.aspp.bottleneck.conv.1", "relu")
-        for i in (4, 3, 2, 1):
-            net[f"dec{i}"] = _Conv(c, sd, f"{p}.dec{i}.conv1.conv.0.weight", f"{p}.dec{i}.conv1.conv.1", "relu", 1, 1)
+            net[f"aspp.conv{j}"] = self._mk(sd, f"{p}.aspp.conv{j}.conv.0.weight", f"{p}.aspp.conv{j}.conv.1", "relu", 1, d, d)
+        net["aspp.bottleneck"] = self._mk(sd, f"{p}.aspp.bottleneck.conv.0.weight", f"{p}.aspp.bottleneck.conv.1", "relu")
+        for i in (4, 3, 2):
+            net[f"dec{i}"] = self._mk(sd, f"{p}.dec{i}.conv1.conv.0.weight", f"{p}.dec{i}.conv1.conv.1", "relu", 1, 1)
+        # dec1 reads 2 nout + 1 upsampled channels (dec2's output and the LSTM module's one) and nout skip channels; in f16 the upsampled
+        # part is widened with zero channels to a multiple of 8, so that the fused decoder input stages 16 bytes at a time
+        cu = 2 * sd[f"{p}.dec1.conv1.conv.0.weight"].shape[0] + 1
+        net["dec1"] = self._mk(sd, f"{p}.dec1.conv1.conv.0.weight", f"{p}.dec1.conv1.conv.1", "relu", 1, 1,
+                               zero_in=(cu, -cu % 8) if self.half else (0, 0))
         # LSTMModule (layers_new.py:108-125)
-        net["lstm.conv"] = _Conv(c, sd, f"{p}.lstm_dec2.conv.conv.0.weight", f"{p}.lstm_dec2.conv.conv.1", "relu")
+        net["lstm.conv"] = self._mk(sd, f"{p}.lstm_dec2.conv.conv.0.weight", f"{p}.lstm_dec2.conv.conv.1", "relu")
         lstm = {}
         for d, sfx in enumerate(("", "_reverse")):
             wih = sd[f"{p}.lstm_dec2.lstm.weight_ih_l0{sfx}"].float()
@@ -452,10 +578,12 @@ class VRNetNew(VRNet):
         return y
 
     def _lstm_module(self, net, h: torch.Tensor) -> torch.Tensor:
-        """h [N, bins, frames, C] -> [N, bins, frames, 1]."""
+        """h [N, bins, frames, C] -> [N, bins, frames, 1].  float32 in either precision: in f16 its convolution reads the half ``h`` and
+        writes float32, and the caller rounds the module's result where it joins dec1's input."""
         ctx = self.ctx
         n, nbins, nframes, _ = h.shape
-        seq = self._conv(net["lstm.conv"], h)[..., 0].permute(2, 0, 1).contiguous()         # [frames, N, bins]
+        conv = self._conv(net["lstm.conv"], h, out_f32=True)
+        seq = conv[..., 0].permute(2, 0, 1).contiguous()                                   # [frames, N, bins]
         hd = net["lstm.hidden"]
         both = ctx.empty((nframes, n, 2 * hd))
         for d in (0, 1):
@@ -467,7 +595,10 @@ class VRNetNew(VRNet):
                                             d * hd, d), "alsep_vr_lstm")
         D = net["dense"]
         out = self._linear(both.reshape(nframes * n, 2 * hd), D["w"], D["scale"], D["shift"], 1)   # [frames * N, bins]
-        return out.reshape(nframes, n, nbins).permute(1, 2, 0).unsqueeze(-1).contiguous()
+        out = out.reshape(nframes, n, nbins).permute(1, 2, 0).unsqueeze(-1).contiguous()
+        if self.half:
+            self._note(net["name"] + ".lstm_dec2.lstm", "lstm", (conv,), out.to(self.adt))
+        return out
 
     def _basenet(self, name, x):
         """nets_new.py:31-47."""
@@ -482,10 +613,8 @@ class VRNetNew(VRNet):
         # ASPP with full dilated convolutions (layers_new.py:73-105); Dropout2d is the identity in eval
         ctx = self.ctx
         b, hh, ww, c = e5.shape
-        cat = ctx.empty((b, hh, ww, 5 * c))
-        pooled = ctx.empty((b, 1, ww, c))
-        ctx.check(ctx.lib.alsep_vr_mean_h(ctx.handle, _lib.ptr(e5), _lib.ptr(pooled), b, hh, ww, c), "alsep_vr_mean_h")
-        self._resize(self._conv(net["aspp.conv1"], pooled), hh, ww, cat, 0)
+        cat = ctx.empty((b, hh, ww, 5 * c), self.adt)
+        self._pooled_branch(net, e5, cat)
         self._conv(net["aspp.conv2"], e5, cat, c)
         for k, j in enumerate((3, 4, 5)):
             self._conv(net[f"aspp.conv{j}"], e5, cat, (2 + k) * c)
@@ -493,12 +622,16 @@ class VRNetNew(VRNet):
         h = self._decoder(net["dec4"], h, e4)
         h = self._decoder(net["dec3"], h, e3)
         h = self._decoder(net["dec2"], h, e2)
-        h = torch.cat([h, self._lstm_module(net, h)], dim=3).contiguous()
+        lo = self._lstm_module(net, h).to(self.adt)               # f16: the module's float32 result rounded where it joins dec1's input
+        parts = [h, lo]
+        if net["dec1"].zero_in[1]:
+            parts.append(torch.zeros(tuple(h.shape[:3]) + (net["dec1"].zero_in[1],), dtype=h.dtype, device=h.device))
+        h = torch.cat(parts, dim=3).contiguous()
         return self._decoder(net["dec1"], h, e1)
 
     def mask_nhwc(self, x: torch.Tensor):
         """x [B, bins >= max_bin, frames, 2] -> (logits [B, max_bin, frames, 2], the cropped input) (nets_new.py:81-105)."""
-        xin = x[:, : self.max_bin].contiguous()
+        xin = x[:, : self.max_bin].to(self.adt).contiguous()      # f16: the one rounding of the input
         bandw = xin.shape[1] // 2
         l1_in, h1_in = xin[:, :bandw].contiguous(), xin[:, bandw:].contiguous()
         l1 = self._conv(self.stg1_low_tail, self._basenet("stg1_low_band_net.0", l1_in))
@@ -508,7 +641,7 @@ class VRNetNew(VRNet):
         h2 = self._basenet("stg2_high_band_net", torch.cat([h1_in, h1], dim=3).contiguous())
         aux2 = torch.cat([l2, h2], dim=1)
         f3 = self._basenet("stg3_full_band_net", torch.cat([xin, aux1, aux2], dim=3).contiguous())
-        return self._conv(self.out, f3)
+        return self._conv(self.out, f3, out_f32=True)
 
     def forward_nhwc(self, x: torch.Tensor, aggressiveness: Optional[dict] = None) -> torch.Tensor:
         """x [B, bins, frames, 2] -> x * mask [B, output_bin, frames, 2] (``predict`` before its offset crop; the new nets
@@ -519,6 +652,7 @@ class VRNetNew(VRNet):
         x = x.contiguous()
         mix = x[:, : self.output_bin].contiguous()
         logit = self.mask_nhwc(x)
+        self._logits_finite = torch.isfinite(logit).all() if self.half else None
         out = ctx.empty(tuple(mix.shape))
         ctx.check(ctx.lib.alsep_vr_mask(ctx.handle, _lib.ptr(logit), _lib.ptr(mix), _lib.ptr(out), mix.shape[0], logit.shape[1],
                                         self.output_bin, mix.shape[2], 2, 0, C.c_float(-1.0)), "alsep_vr_mask")

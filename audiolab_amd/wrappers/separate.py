@@ -79,7 +79,8 @@ class Separate(BaseWrapper):
     }
     ENGINE_KNOBS = {"precision": "fp16", "chunker": "ola", "overlap": 0.25, "num_gpus": 1}
 
-    # further engine-level options (a pre-built engine under "separator", ensemble_strength, ...) reach separate_music when set here
+    # further engine-level options (a pre-built engine under "separator", ensemble_strength, vr_precision="f16", ...) reach separate_music
+    # when set here
     engine_options: Dict[str, Any] = {}
 
     def process_audio(self, inputs: List[ProjectFiles], callback=None, **kwargs: Dict[str, Any]) -> List[ProjectFiles]:
@@ -119,6 +120,8 @@ class Separate(BaseWrapper):
                 val = filtered_kwargs.get(knob, self.engine_options.get(knob, dflt))
                 if knob != "num_gpus" and val != dflt:
                     current_config[knob] = val
+            if self.engine_options.get("vr_precision", "f32") != "f32":      # engine_options only: not one of the hidden inputs
+                current_config["vr_precision"] = self.engine_options["vr_precision"]
             eng = self.engine_options.get("separator")
             if eng is not None and getattr(eng, "allow_synthetic", False):
                 # stems made from random-init weights (bench / tests) must never satisfy a later run with real models;

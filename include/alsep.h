@@ -457,6 +457,23 @@ int alsep_nn_norm_h(alsep_ctx* ctx, const float* x, void* y, int y_f16, const fl
 int alsep_nn_xattention_f16(alsep_ctx* ctx, const void* q, const void* kv, void* out, int n_seq, int Lq, int Lk, int heads, int dim_head,
                             int64_t q_seq_stride, int64_t q_row_stride, int64_t kv_seq_stride, int64_t kv_row_stride, int64_t o_seq_stride,
                             int64_t o_row_stride, float scale);
+/* VR networks, half-precision mode (csrc/vrnet_h.h): channels-last IEEE half tensors.
+ * alsep_vr_conv2d on the f16 matrix pipe: x [B, H, W, Cin] half, w [Cout][Kp] half with k = (dy, dx, ci) zero-padded from KH KW Cin to Kp (a
+ * multiple of 32), y [B, Ho, Wo, y_ctotal] at channel y_coff = act(conv * scale + shift), half (y_f16) or float32; act 0 / 1 ReLU / 2 LeakyReLU */
+int alsep_vr_conv_h(alsep_ctx* ctx, const void* x, const void* w, const float* scale, const float* shift, void* y, int y_f16, int64_t B, int H,
+                    int W, int Cin, int Cout, int Kp, int KH, int KW, int stride, int pad_h, int pad_w, int dil_h, int dil_w, int act,
+                    int y_ctotal, int y_coff);
+/* The decoder's convolution without its concatenated input: channels [0, Cu) are x [B, Hu, Wu, Cu] resized x2 (bilinear, align_corners;
+ * float32 arithmetic, rounded to half: the bits of alsep_vr_resize_bilinear_h), channels [Cu, Cu + Cs) are skip [B, 2 Hu, Ws, Cs] at columns
+ * w_off .. w_off + 2 Wu - 1.  KH x KW, stride 1, padding pad; everything else as alsep_vr_conv_h. */
+int alsep_vr_decoder_conv_h(alsep_ctx* ctx, const void* x, const void* skip, const void* w, const float* scale, const float* shift, void* y,
+                            int y_f16, int64_t B, int Hu, int Wu, int Cu, int Ws, int Cs, int w_off, int Cout, int Kp, int KH, int KW, int pad,
+                            int act, int y_ctotal, int y_coff);
+/* alsep_vr_depthwise / _resize_bilinear / _copy_slice / _mean_h on half tensors (depthwise weights half; float32 arithmetic) */
+int alsep_vr_depthwise_h(alsep_ctx* ctx, const void* x, const void* w, void* y, int64_t B, int H, int W, int C, int KH, int KW, int pad, int dil);
+int alsep_vr_resize_bilinear_h(alsep_ctx* ctx, const void* x, void* y, int64_t B, int H, int W, int C, int Ho, int Wo, int y_ctotal, int y_coff);
+int alsep_vr_copy_slice_h(alsep_ctx* ctx, const void* x, void* y, int64_t BH, int Wx, int C, int w_off, int Wy, int y_ctotal, int y_coff);
+int alsep_vr_mean_hh(alsep_ctx* ctx, const void* x, void* y, int64_t B, int H, int W, int C);
 /* Roformer band split, input side, all bands in one launch: feat[band][t][kmax] (half) = RMSNorm over the band's `width[band]` gathered
  * spectrogram values of frame t (spec [4][F][T]; pidx[band][kmax / 2] merged bin index 2 f + s or -1; gamma[band][kmax]), zero-padded */
 int alsep_roformer_bandsplit_in(alsep_ctx* ctx, const float* spec, const int* pidx, const float* gamma, const int* width, void* feat, int nb,
