@@ -2099,6 +2099,259 @@ tdf_bf16_wide_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const
 }
 
 // ------------------------------------------------------------------------------------------
+// Residual TDF linear of levels 0 and 1, persistent over the row blocks (C = 48 or 96, M multiple of 384, K = 64 NT): same
+// math, k order and epilogue arithmetic as tdf_bf16_wide_kernel<4, true>, different traffic.  A work item is two consecutive
+// units x ALL M rows; workgroups stride statically over the items (no atomics, no hand-off between workgroups).
+//   * the item's hidden activations [NT][2 units][64 f][48 c] (72 KiB at K = 384) come into LDS ONCE by LDS-DMA and stay
+//     there; the wide kernel streams them through its ring once per 192-row block, 16 times at level 0 -- L2 -> LDS traffic
+//     as large as the launch's whole HBM traffic;
+//   * after that fill the waves never meet again inside the item: wave w walks the 48-row blocks w, w + 8, ... on its own
+//     (weights straight into registers two K tiles ahead, three buffers; K tiles are a multiple of three, so the buffer of a
+//     tile is the same in every row block and the first two tiles of the next row block are requested under the last MFMAs
+//     of this one), so one wave's epilogue runs beside another wave's MFMAs;
+//   * the residual rows and the bias of a row block are requested behind the weight loads of its first K tile: their HBM
+//     latency sits under that row block's MFMAs (acc 2 x 3 x 3 = 72 VGPRs leaves room for the 40 they take);
+//   * BN scale / shift of the two units (the same for every item: C / 48 is 1 or 2) are read from LDS, not from memory;
+//   * FINAL: as in the wide kernel; the rounded rows reuse the wave's fp32 staging rows (read whole, then overwritten).
+// LDS: 72 KiB tile + 8 x 9.75 KiB staging + 0.75 KiB scale/shift (+ 6 KiB final weights) = 156.75 KiB: one workgroup of
+// eight waves per CU, two waves per SIMD.
+// ------------------------------------------------------------------------------------------
+struct TdfPersist {
+    static constexpr int WV = 8, TR = 48, BM = TR * WV, UN = 2, UC = 48, BK = 64;
+    static constexpr int THREADS = 64 * WV;
+    static constexpr int STAGE_ELEMS = UN * BK * UC;                 // one K tile of both units: 12 KiB
+    static constexpr int SS = TdfWide<4>::SS, FS = TdfWide<4>::FS, FWN = TdfWide<4>::FWN;
+    static constexpr size_t stage_bytes = (size_t)WV * TR * SS * sizeof(float);
+    static constexpr size_t bn_bytes = (size_t)UN * 2 * UC * sizeof(float);
+    static constexpr size_t tile_bytes(int nt) { return (size_t)nt * STAGE_ELEMS * sizeof(bf16_t); }
+    static constexpr size_t lds_bytes(int nt, bool fin) { return tile_bytes(nt) + stage_bytes + bn_bytes + (fin ? WV * FWN * sizeof(float) : 0); }
+    static_assert((size_t)TR * FS * sizeof(bf16_t) <= (size_t)TR * SS * sizeof(float), "FINAL: the rounded rows fit in the staging rows");
+};
+
+// glds16 with the source as wave-uniform global base + 32-bit lane offset (one address VGPR, no 64-bit lane pointer)
+__device__ __forceinline__ void glds16_base(const ALSEP_GLOBAL char* gbase, unsigned lane_off, void* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((const ALSEP_GLOBAL void*)(gbase + lane_off), (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
+template <int NT, bool FINAL>
+__global__ void __launch_bounds__(TdfPersist::THREADS, 1)
+tdf_bf16_persist_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf16_t* __restrict__ Wf,
+                        const float* __restrict__ bias, const float* __restrict__ scale, const float* __restrict__ shift,
+                        const bf16_t* __restrict__ R, int M, int64_t nitems, int C,
+                        const float* __restrict__ FW, const float* __restrict__ FB, bf16_t* __restrict__ FOUT, float falpha) {
+    typedef TdfPersist Tc;
+    static_assert(NT % 3 == 0 && NT >= 3, "three weight buffers: a K tile's buffer is the same in every row block");
+    static_assert(Tc::lds_bytes(NT, FINAL) <= 160 * 1024, "LDS of a CU");
+    constexpr int K = NT * Tc::BK;
+    bf16_t* tile = reinterpret_cast<bf16_t*>(alsep_smem);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, lq = lane >> 4;
+    float* stg = reinterpret_cast<float*>(alsep_smem + Tc::tile_bytes(NT)) + (size_t)wave * (Tc::TR * Tc::SS);
+    bf16_t* frow = reinterpret_cast<bf16_t*>(stg);                   // FINAL only: over the staging rows, once they are read
+    float* bnl = reinterpret_cast<float*>(alsep_smem + Tc::tile_bytes(NT) + Tc::stage_bytes);     // [unit][scale | shift][48]
+    float* fwl = bnl + Tc::UN * 2 * Tc::UC + wave * Tc::FWN;         // FINAL only
+    const int ush = C / Tc::UC - 1;                                  // units per frame 1 or 2 (launcher), as a shift: unit u of every item has
+                                                                     // channel base (u & ush) * 48 and frame (u0 + u) >> ush
+    const int nrb = M / Tc::BM;
+
+    if (tid < Tc::UN * 2 * Tc::UC) {
+        const int u = tid / (2 * Tc::UC), which = (tid / Tc::UC) & 1, c = tid % Tc::UC;
+        bnl[tid] = (which ? shift : scale)[(u & ush) * Tc::UC + c];
+    }
+    float fbs[4];
+    if (FINAL) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) fwl[j * 64 + lane] = FW[j * 64 + lane];     // wave-private, read after this wave's first wave barrier
+#pragma unroll
+        for (int r = 0; r < 4; ++r) fbs[r] = FB[r];
+    }
+    // 48 rows x 6 groups of 8 channels = 288 16-byte output groups per unit, 5 per lane (the last one half-filled)
+    unsigned loff[5], xoff[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int within = j * 64 + lane;
+        xoff[j] = (unsigned)(((within / 6) * C + (within % 6) * 8) * (int)sizeof(bf16_t));
+    }
+#pragma unroll
+    for (int it = 0; it < 5; ++it) {
+        const int gidx = it * 64 + lane;
+        loff[it] = (unsigned)(((gidx / 6) * C + (gidx % 6) * 8) * (int)sizeof(bf16_t));
+    }
+    const unsigned woff = (unsigned)lane * 16u;
+    const int trow = l15 >> 2, tcol = (l15 & 3) * 4;
+    const bf16_t* xlane = tile + (4 * lq + trow) * Tc::UC + tcol;
+
+    bf16x8 wf[3][2][3];                                              // [K tile % 3][k-step][m-tile]
+    auto load_w = [&](int buf, int rowblk, int it) {                 // 6 KiB contiguous per wave and K tile (make_tdf_frag_weights)
+        const ALSEP_GLOBAL char* wp = opaque_uniform_gptr(reinterpret_cast<const char*>(Wf) + ((size_t)rowblk * NT + it) * (6 * 1024));
+#pragma unroll
+        for (int i = 0; i < 6; ++i) wf[buf][i / 3][i % 3] = *reinterpret_cast<const ALSEP_GLOBAL bf16x8*>(wp + woff + i * 1024);
+    };
+
+    for (int64_t item = blockIdx.x; item < nitems; item += gridDim.x) {
+        const int64_t u0 = item * Tc::UN;
+        load_w(0, wave, 0);
+        load_w(1, wave, 1);
+        barrier_nodrain();                                           // every wave has left the previous item's tile (first item: bnl is written)
+        // fill: 12 NT pieces of 1 KiB, piece p = ((K tile * 2 + unit) * 6 + j) lands at p KiB; three pieces are 32 rows of 96 bytes
+        constexpr int NP = NT * Tc::UN * 6;
+#pragma unroll 1                                             // rolled: unrolled, the nine 64-bit lane addresses are hoisted out of the item loop and spill
+        for (int p = wave; p < NP; p += Tc::WV) {
+            {
+                const int tu = p / 6, j = p % 6, it = tu / Tc::UN, u = tu % Tc::UN;
+                const ALSEP_GLOBAL char* src = opaque_uniform_gptr(reinterpret_cast<const char*>(
+                    X + (((u0 + u) >> ush) * K + it * Tc::BK + (j / 3) * 32) * (int64_t)C + (u & ush) * Tc::UC));
+                const int j3 = j % 3;
+                glds16_base(src, j3 == 0 ? xoff[0] : (j3 == 1 ? xoff[1] : xoff[2]), tile + (size_t)p * 64 * 8);
+            }
+        }
+        wait_vmcnt<0>();
+        barrier_nodrain();                                           // every wave's pieces have landed
+
+        for (int rb = 0; rb < nrb; ++rb) {
+            const int rowblk = rb * Tc::WV + wave;                   // 48-row block of the weight matrix
+            const int rownext = (rb + 1 < nrb ? rb + 1 : rb) * Tc::WV + wave;      // last row block: a harmless reload instead of a branch
+            auto unit_base = [&](int u) {
+                return (((u0 + u) >> ush) * M + rowblk * Tc::TR) * (int64_t)C + (u & ush) * Tc::UC;
+            };
+            f32x4 acc[Tc::UN][3][3];
+#pragma unroll
+            for (int u = 0; u < Tc::UN; ++u)
+#pragma unroll
+                for (int ni = 0; ni < 3; ++ni)
+#pragma unroll
+                    for (int mi = 0; mi < 3; ++mi) acc[u][ni][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+            bf16x8 rr[Tc::UN][5];
+            float bvv[3];
+            bf16x8 xa[3], xb[3];
+            auto mma_unit = [&](int u, const bf16x8 (&xf)[3], int buf, int ks) {
+#pragma unroll
+                for (int ni = 0; ni < 3; ++ni)
+#pragma unroll
+                    for (int mi = 0; mi < 3; ++mi) mma_step(acc[u][ni][mi], xf[ni], wf[buf][ks][mi]);
+            };
+#pragma unroll
+            for (int it = 0; it < NT; ++it) {
+                if (it + 2 < NT) load_w((it + 2) % 3, rowblk, it + 2);
+                else load_w((it + 2) % 3, rownext, it + 2 - NT);
+                if (it == 0) {                                       // behind W(2): the waits for W(0) and W(1) leave these in flight
+                    // FINAL has no register to keep these two lane offsets across the loops (they spilled): recomputed per row block
+                    const int ln = FINAL ? opaque_vgpr(lane) : lane;
+                    const unsigned roff4 = FINAL ? (unsigned)((((256 + ln) / 6) * C + ((256 + ln) % 6) * 8) * (int)sizeof(bf16_t)) : loff[4];
+                    const unsigned boff = (unsigned)((ln & 15) * (int)sizeof(float));
+#pragma unroll
+                    for (int u = 0; u < Tc::UN; ++u) {
+                        const ALSEP_GLOBAL char* rp = opaque_uniform_gptr(reinterpret_cast<const char*>(R + unit_base(u)));
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) rr[u][g] = *reinterpret_cast<const ALSEP_GLOBAL bf16x8*>(rp + loff[g]);
+                        if (lane < Tc::TR * 6 - 256) rr[u][4] = *reinterpret_cast<const ALSEP_GLOBAL bf16x8*>(rp + roff4);
+                    }
+#pragma unroll
+                    for (int mi = 0; mi < 3; ++mi) bvv[mi] = 0.f;
+                    if (bias) {                                      // scalar base + 32-bit lane offset: no 64-bit lane pointer kept across the loops
+                        const ALSEP_GLOBAL char* bp = opaque_uniform_gptr(reinterpret_cast<const char*>(bias + rowblk * Tc::TR));
+#pragma unroll
+                        for (int mi = 0; mi < 3; ++mi)
+                            bvv[mi] = *reinterpret_cast<const ALSEP_GLOBAL float*>(bp + boff + mi * 16 * (int)sizeof(float));
+                    }
+                }
+                const bf16_t* xs = xlane + (size_t)it * Tc::STAGE_ELEMS;
+                if (it == 0) {
+                    tdfw_read_x<0, 0>(xa, xs);
+                    tdfw_read_x<0, 1>(xb, xs);
+                }
+                lds_read_tr16_wait_n<6>();  mma_unit(0, xa, it % 3, 0);
+                tdfw_read_x<1, 0>(xa, xs);
+                lds_read_tr16_wait_n<6>();  mma_unit(1, xb, it % 3, 0);
+                tdfw_read_x<1, 1>(xb, xs);
+                if (it + 1 < NT) {                                   // the next K tile's first fragments: the tile is resident, nothing to wait for
+                    lds_read_tr16_wait_n<6>();  mma_unit(0, xa, it % 3, 1);
+                    tdfw_read_x<0, 0>(xa, xs + Tc::STAGE_ELEMS);
+                    lds_read_tr16_wait_n<6>();  mma_unit(1, xb, it % 3, 1);
+                    tdfw_read_x<0, 1>(xb, xs + Tc::STAGE_ELEMS);
+                } else {
+                    lds_read_tr16_wait_n<6>();  mma_unit(0, xa, it % 3, 1);
+                    lds_read_tr16_wait_n<0>();  mma_unit(1, xb, it % 3, 1);
+                }
+            }
+
+            // Epilogue of this wave's 48 rows, one unit at a time through its private staging rows: arithmetic exactly as in
+            // tdf_bf16_wide_kernel (bias, BN, ReLU and the residual add in fp32, one rounding).
+#pragma unroll
+            for (int u = 0; u < Tc::UN; ++u) {
+                ALSEP_GLOBAL char* yb = const_cast<ALSEP_GLOBAL char*>(opaque_uniform_gptr(reinterpret_cast<const char*>(Y + unit_base(u))));
+#pragma unroll
+                for (int ni = 0; ni < 3; ++ni) {
+                    const f32x4 sc = *reinterpret_cast<const f32x4*>(bnl + u * 2 * Tc::UC + ni * 16 + 4 * lq);
+                    const f32x4 sh = *reinterpret_cast<const f32x4*>(bnl + u * 2 * Tc::UC + Tc::UC + ni * 16 + 4 * lq);
+#pragma unroll
+                    for (int mi = 0; mi < 3; ++mi) {
+                        f32x4 v;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = fmaxf(fmaf(acc[u][ni][mi][r] + bvv[mi], sc[r], sh[r]), 0.f);
+                        *reinterpret_cast<f32x4*>(stg + (mi * 16 + l15) * Tc::SS + ni * 16 + 4 * lq) = v;
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+                bf16x8 q[5];
+#pragma unroll
+                for (int g = 0; g < 5; ++g) {
+                    const int gidx = g * 64 + lane;
+                    const int fr = gidx / 6, cg = gidx % 6;
+                    if (gidx < Tc::TR * 6) {
+                        const f32x4 lo = *reinterpret_cast<const f32x4*>(stg + fr * Tc::SS + cg * 8);
+                        const f32x4 hi = *reinterpret_cast<const f32x4*>(stg + fr * Tc::SS + cg * 8 + 4);
+                        float y[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) y[e] += (float)rr[u][g][e];
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) q[g][e] = (bf16_t)y[e];
+                        if (!FINAL) stream_store(reinterpret_cast<ALSEP_GLOBAL bf16x8*>(yb + loff[g]), q[g]);
+                    }
+                }
+                __builtin_amdgcn_wave_barrier();
+                if (FINAL) {
+                    // every staging row is read: the rounded rows [48 f'][48 c] (row stride FS) take their place, then the chains
+                    // of final_conv_kernel as in the wide kernel -- lane = f' row = one pixel of frame u0 + u (C == 48)
+#pragma unroll
+                    for (int g = 0; g < 5; ++g) {
+                        const int gidx = g * 64 + lane;
+                        if (gidx < Tc::TR * 6) *reinterpret_cast<bf16x8*>(frow + (gidx / 6) * Tc::FS + (gidx % 6) * 8) = q[g];
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    const int ln = opaque_vgpr(lane);                // recomputed here, not kept (or spilled) across the k loop
+                    const int frl = ln < Tc::TR ? ln : Tc::TR - 1;
+                    float y[4] = {fbs[0], fbs[1], fbs[2], fbs[3]};
+#pragma unroll 2
+                    for (int ci = 0; ci < Tc::UC; ci += 8) {
+                        const bf16x8 xv = *reinterpret_cast<const bf16x8*>(frow + frl * Tc::FS + ci);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const f32x4 w0 = *reinterpret_cast<const f32x4*>(fwl + r * Tc::UC + ci);
+                            const f32x4 w1 = *reinterpret_cast<const f32x4*>(fwl + r * Tc::UC + ci + 4);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) y[r] = fmaf(w0[e], (float)xv[e], y[r]);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) y[r] = fmaf(w1[e], (float)xv[4 + e], y[r]);
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) y[r] *= falpha;
+                    ALSEP_GLOBAL char* fo = const_cast<ALSEP_GLOBAL char*>(
+                        opaque_uniform_gptr(reinterpret_cast<const char*>(FOUT + (((u0 + u) * M + rowblk * Tc::TR) << 2))));
+                    bf16x4 yq;                                       // one rounding, as store4
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) yq[r] = (bf16_t)y[r];
+                    if (ln < Tc::TR) *reinterpret_cast<ALSEP_GLOBAL bf16x4*>(fo + (unsigned)ln * (4u * (unsigned)sizeof(bf16_t))) = yq;
+                    __builtin_amdgcn_wave_barrier();                 // the next unit's staging rows overwrite these
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // bf16 ds (2x2/2 conv, 48 -> 96) and us (2x2 transposed conv, 96 -> 48, * skip) between levels 0 and 1,
 // the two largest resampling layers.  Every input element feeds exactly one output pixel (no halo,
 // no reuse), so nothing is staged: a wave keeps its weight fragments in registers for its whole
@@ -3432,6 +3685,50 @@ int tdf_final_mode() {
     static const int v = [] { const char* e = getenv("ALSEP_TDF_FINAL"); return e ? atoi(e) : 1; }();
     return v;
 }
+// ALSEP_TDF_PERSIST: 1 (default) = the residual linear of levels 0 and 1 runs on tdf_bf16_persist_kernel for the launch kinds
+// in kTdfPersistRouted (each kind is routed there only where it measured faster than the wide kernel on the same box:
+// profiles/tdf_persist_kernel_stats.txt); 0 = never (the wide kernel, as before); 2 = every kind the kernel serves
+// (measurements, tests).  ALSEP_TDF_PERSIST_GRID=n caps its grid (tests: several items per workgroup at small shapes).
+enum { kTdfPersistK384 = 1, kTdfPersistK192 = 2, kTdfPersistFinal = 4 };
+constexpr int kTdfPersistRouted = kTdfPersistK384 | kTdfPersistK192 | kTdfPersistFinal;
+int tdf_persist_mode() {
+    static const int v = [] { const char* e = getenv("ALSEP_TDF_PERSIST"); return e ? atoi(e) : 1; }();
+    return v;
+}
+template <int NT, bool FINAL>
+void launch_tdf_persist_inst(alsep_ctx* ctx, hipError_t& attr, unsigned grid, const GemmLayer& L, const bf16_t* X, bf16_t* Y,
+                             const bf16_t* R, int64_t nitems, int C, const FinalFold* fin) {
+    constexpr int lds = (int)TdfPersist::lds_bytes(NT, FINAL);
+    attr = hipFuncSetAttribute((const void*)tdf_bf16_persist_kernel<NT, FINAL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (attr != hipSuccess) return;
+    hipLaunchKernelGGL((tdf_bf16_persist_kernel<NT, FINAL>), dim3(grid), dim3(TdfPersist::THREADS), lds, ctx->stream, X, Y,
+                       (const bf16_t*)L.wwide.p, L.has_bias ? (const float*)L.bias.p : nullptr, (const float*)L.scale.p,
+                       (const float*)L.shift.p, R, L.M, nitems, C, fin ? fin->w : nullptr, fin ? fin->b : nullptr,
+                       fin ? (bf16_t*)fin->out : nullptr, fin ? fin->alpha : 0.f);
+}
+// caller: R != nullptr, M % 384 == 0, K 384 or 192, C 48 or 96, nunits % 4 == 0, inside its ProfScope; fin only where C == 48
+int launch_tdf_persist(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* R, int64_t nunits, int C,
+                       FinalFold* fin) {
+    static const int cap = [] { const char* e = getenv("ALSEP_TDF_PERSIST_GRID"); return e ? atoi(e) : 0; }();
+    const int64_t nitems = nunits / TdfPersist::UN;
+    int64_t grid = device_cu_count(ctx);                             // 156.75 KiB of LDS: one workgroup per CU
+    if (cap > 0 && cap < grid) grid = cap;
+    if (nitems < grid) grid = nitems;
+    hipError_t attr = hipSuccess;
+    if (fin && L.K == 384) launch_tdf_persist_inst<6, true>(ctx, attr, (unsigned)grid, L, X, Y, R, nitems, C, fin);
+    else if (fin) launch_tdf_persist_inst<3, true>(ctx, attr, (unsigned)grid, L, X, Y, R, nitems, C, fin);
+    else if (L.K == 384) launch_tdf_persist_inst<6, false>(ctx, attr, (unsigned)grid, L, X, Y, R, nitems, C, nullptr);
+    else launch_tdf_persist_inst<3, false>(ctx, attr, (unsigned)grid, L, X, Y, R, nitems, C, nullptr);
+    ALSEP_HIP(ctx, attr);
+    if (fin) {
+        fin->done = true;
+        note_launch(ctx, "tdf_bf16_wide_kernel<res,final>");
+    }
+    note_launch(ctx, "tdf_bf16_wide_kernel<res>");                   // one per layer launch, whichever instance serves it
+    ALSEP_LAUNCH_CHECK(ctx, "tdf_bf16_persist_kernel");
+    return ALSEP_OK;
+}
+
 template <int WM>
 int launch_tdf_wide(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* R, int64_t nunits, int C,
                     FinalFold* fin) {
@@ -3445,7 +3742,15 @@ int launch_tdf_wide(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t*
     const dim3 grid = nyb ? dim3((unsigned)(gx * nrb)) : dim3((unsigned)gx, nrb);
     ProfScope prof(ctx, ALSEP_PROF_TDF);
     static const int rpf = [] { const char* e = getenv("ALSEP_TDF_RPF"); return e ? atoi(e) : 2; }();
-    if (WM == 4 && R && rpf != 0 && fin && C == Tc::UC && tdf_final_mode()) {
+    const bool fold = WM == 4 && R && rpf != 0 && fin && C == Tc::UC && tdf_final_mode();
+    if (WM == 4 && R && rpf != 0 && tdf_wide_mode() == 1 && L.M % TdfPersist::BM == 0 && (C == Tc::UC || C == 2 * Tc::UC) &&
+        (L.K == 384 || L.K == 192)) {
+        const int kind = fold ? kTdfPersistFinal : (L.K == 384 ? kTdfPersistK384 : kTdfPersistK192);
+        const int mode = tdf_persist_mode();
+        if (mode >= 2 || (mode == 1 && (kTdfPersistRouted & kind)))
+            return launch_tdf_persist(ctx, L, X, Y, R, nunits, C, fold ? fin : nullptr);
+    }
+    if (fold) {
         ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)tdf_bf16_wide_kernel<4, true, 2, true>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)TdfWide<4>::lds_bytes));
         hipLaunchKernelGGL((tdf_bf16_wide_kernel<4, true, 2, true>), grid, dim3(TdfWide<4>::THREADS), TdfWide<4>::lds_bytes,
