@@ -183,6 +183,10 @@ _SIGNATURES = {
     "alsep_rfft_mag_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "alsep_dft_f64_workspace_bytes": (C.c_int64, [C.c_int64]),
     "alsep_dft_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64]),
+    "alsep_reverb_apply_block_log2": (C.c_int, [C.c_int64, C.c_int]),
+    "alsep_reverb_apply_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "alsep_reverb_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int,
+                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "alsep_nn_lstm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "alsep_nn_localstate_softmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]),
     "alsep_nn_blstm_unfold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int] * 5),

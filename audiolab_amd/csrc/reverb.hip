@@ -353,6 +353,114 @@ int64_t dft_ws_points(int64_t n) {
 
 constexpr int64_t kMaxPoints = (int64_t)1 << 27;                            // 2^27 complex doubles = 2 GiB per buffer
 
+// ---- convolution reverb (apply_reverb, reverb.py:179-209): overlap-save blocks of F = 2^k points, S = F - L + 1 new samples each --------
+// One batched Stockham pass: fft_pass_kernel over `blocks` consecutive F-point arrays (block b at in + b n, out + b n).  Same butterfly,
+// same twiddles, so a block's transform does not depend on which batch it travels in.
+template <int R>
+__global__ void __launch_bounds__(kRvThreads)
+fft_pass_batched_kernel(const cplx* __restrict__ in, cplx* __restrict__ out, int log2n, int64_t ns, double sign, int64_t blocks) {
+    const int log2m = log2n - (R == 8 ? 3 : R == 4 ? 2 : 1);
+    const int64_t m = (int64_t)1 << log2m, total = blocks << log2m;
+    for (int64_t i = (int64_t)blockIdx.x * kRvThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kRvThreads) {
+        const int64_t base = (i >> log2m) << log2n, j = i & (m - 1), k = j & (ns - 1);
+        cplx v[R];
+#pragma unroll
+        for (int t = 0; t < R; ++t) v[t] = in[base + j + t * m];
+        if (ns > 1) {
+#pragma unroll
+            for (int t = 1; t < R; ++t) v[t] = cmul(v[t], unit_root(((int64_t)t * k) % (ns * R), ns * R, sign));
+        }
+        dft_small<R>(v, sign);
+        const int64_t j0 = base + (j - k) * R + k;
+#pragma unroll
+        for (int t = 0; t < R; ++t) out[j0 + t * ns] = v[t];
+    }
+}
+
+// the impulse response as a complex F-point signal, zero-padded and scaled by 1 / F (a power of two: exact), ready for fft_pow2
+__global__ void __launch_bounds__(kRvThreads)
+ir_pad_kernel(const double* __restrict__ ir, int64_t n_ir, double scale, cplx* __restrict__ z, int64_t F) {
+    for (int64_t j = (int64_t)blockIdx.x * kRvThreads + threadIdx.x; j < F; j += (int64_t)gridDim.x * kRvThreads)
+        z[j] = {j < n_ir ? ir[j] * scale : 0.0, 0.0};
+}
+
+// blocks b0 .. b0 + blocks of the channel pair (x0, x1): z[b][p] = x0[s] + i x1[s], s = (b0 + b) S + p - (L - 1); zero outside [0, n)
+// and for a missing second channel
+__global__ void __launch_bounds__(kRvThreads)
+ola_gather_kernel(const float* __restrict__ x0, const float* __restrict__ x1, int64_t n, cplx* __restrict__ z, int log2F, int64_t S, int64_t L,
+                  int64_t b0, int64_t blocks) {
+    const int64_t F = (int64_t)1 << log2F, total = blocks << log2F;
+    for (int64_t i = (int64_t)blockIdx.x * kRvThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kRvThreads) {
+        const int64_t s = (b0 + (i >> log2F)) * S + (i & (F - 1)) - (L - 1);
+        cplx v = {0.0, 0.0};
+        if (s >= 0 && s < n) v = {(double)x0[s], x1 ? (double)x1[s] : 0.0};
+        z[i] = v;
+    }
+}
+
+// every block's spectrum times the (pre-scaled) spectrum of the impulse response
+__global__ void __launch_bounds__(kRvThreads)
+ola_product_kernel(cplx* __restrict__ z, const cplx* __restrict__ h, int log2F, int64_t blocks) {
+    const int64_t F = (int64_t)1 << log2F, total = blocks << log2F;
+    for (int64_t i = (int64_t)blockIdx.x * kRvThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kRvThreads) z[i] = cmul(z[i], h[i & (F - 1)]);
+}
+
+__device__ __forceinline__ float clip_unit(double v) { return (float)(v < -1.0 ? -1.0 : v > 1.0 ? 1.0 : v); }   // np.clip: NaN passes
+
+// np.pad(wet, (pre, 0))[:n], dry + gain * wet, np.clip (:197-198, :205-206): block b's outputs L-1 .. F-1 are convolution samples
+// t = (b0 + b) S + q, q < S, which land at o = t + pre; re -> channel 0 of the pair, im -> channel 1
+__global__ void __launch_bounds__(kRvThreads)
+ola_finish_kernel(const cplx* __restrict__ z, const float* __restrict__ x0, const float* __restrict__ x1, float* __restrict__ y0,
+                  float* __restrict__ y1, int64_t n, int log2F, int64_t S, int64_t L, int64_t pre, double gain, int64_t b0, int64_t blocks) {
+    const int64_t total = blocks * S;
+    for (int64_t i = (int64_t)blockIdx.x * kRvThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kRvThreads) {
+        const int64_t b = i / S, q = i - b * S, o = (b0 + b) * S + q + pre;
+        if (o >= n) continue;
+        const cplx w = z[(b << log2F) + (L - 1) + q];
+        y0[o] = clip_unit((double)x0[o] + gain * w.x);
+        if (y1) y1[o] = clip_unit((double)x1[o] + gain * w.y);
+    }
+}
+
+// the first min(pre, n) samples, where the padded wet signal is zero: clip(dry), all channels
+__global__ void __launch_bounds__(kRvThreads)
+ola_head_kernel(const float* __restrict__ x, float* __restrict__ y, int channels, int64_t ld, int64_t ld_out, int64_t head) {
+    const int64_t total = (int64_t)channels * head;
+    for (int64_t i = (int64_t)blockIdx.x * kRvThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kRvThreads) {
+        const int64_t c = i / head, o = i - c * head;
+        y[c * ld_out + o] = clip_unit((double)x[c * ld + o]);
+    }
+}
+
+int fft_pow2_batched(alsep_ctx* ctx, cplx* a, cplx* b, int log2n, double sign, int64_t blocks, cplx** res) {
+    int64_t ns = 1;
+    int left = log2n;
+    cplx *src = a, *dst = b;
+    while (left > 0) {
+        const int r = left >= 3 ? 3 : left;
+        const dim3 grid(rv_grid(blocks << (log2n - r))), block(kRvThreads);
+        if (r == 3) hipLaunchKernelGGL(fft_pass_batched_kernel<8>, grid, block, 0, ctx->stream, src, dst, log2n, ns, sign, blocks);
+        else if (r == 2) hipLaunchKernelGGL(fft_pass_batched_kernel<4>, grid, block, 0, ctx->stream, src, dst, log2n, ns, sign, blocks);
+        else hipLaunchKernelGGL(fft_pass_batched_kernel<2>, grid, block, 0, ctx->stream, src, dst, log2n, ns, sign, blocks);
+        ALSEP_LAUNCH_CHECK(ctx, "fft_pass_batched_kernel");
+        ns <<= r;
+        left -= r;
+        cplx* t = src; src = dst; dst = t;
+    }
+    *res = src;
+    return ALSEP_OK;
+}
+
+constexpr int64_t kMaxIrTaps = (int64_t)1 << 20;                            // 21.8 s at 48 kHz; blocks of at most 2^21 points (32 MiB)
+
+// the block exponent k (F = 2^k >= 2 L): the caller's, or max(ceil(log2(2 L)), 10) for log2_block = 0; -1 = bad geometry
+int ola_block_log2(int64_t n_ir, int log2_block) {
+    if (n_ir < 1 || n_ir > kMaxIrTaps || log2_block < 0) return -1;
+    const int need = log2_ceil(2 * n_ir);
+    if (log2_block == 0) return need < 10 ? 10 : need;
+    return (log2_block < need || log2_block > 21) ? -1 : log2_block;
+}
+
 }  // namespace
 
 extern "C" int64_t alsep_dft_f64_workspace_bytes(int64_t n) {
@@ -474,6 +582,73 @@ extern "C" int alsep_rfft_mag_f64(alsep_ctx* ctx, const double* x, int64_t n, vo
     if (int rc = dft_impl(ctx, z, s, n, -1.0, s + n)) return rc;
     hipLaunchKernelGGL(magnitude_kernel, dim3(rv_grid(n / 2 + 1)), dim3(kRvThreads), 0, ctx->stream, s, mag_out, n / 2 + 1);
     ALSEP_LAUNCH_CHECK(ctx, "rfft_mag_kernel");
+    return ALSEP_OK;
+}
+
+extern "C" int alsep_reverb_apply_block_log2(int64_t n_ir, int log2_block) { return ola_block_log2(n_ir, log2_block); }
+
+extern "C" int64_t alsep_reverb_apply_workspace_bytes(int64_t n_ir, int log2_block, int blocks_per_batch) {
+    const int k = ola_block_log2(n_ir, log2_block);
+    if (k < 0 || blocks_per_batch < 1) return -1;
+    return (1 + 2 * (int64_t)blocks_per_batch) * ((int64_t)sizeof(cplx) << k);   // the IR's spectrum + two buffers per block
+}
+
+// apply_reverb's arithmetic (reverb.py:186-206): out = clip(dry + wet_gain * pad(fftconvolve(dry_c, ir, "full"), (pre, 0))[:n], -1, 1) per
+// channel by overlap-save in double precision; channels travel in pairs as re / im of one complex signal (the IR is real).
+extern "C" int alsep_reverb_apply(alsep_ctx* ctx, const float* dry, int channels, int64_t n, int64_t ld, const double* ir, int64_t n_ir,
+                                  int64_t pre_delay_samples, double wet_gain, int log2_block, float* out, int64_t ld_out, void* ws,
+                                  int64_t ws_bytes) {
+    ALSEP_ENTER(ctx);
+    if (!ctx || !dry || !ir || !out || !ws || channels < 1 || n < 1 || ld < n || ld_out < n || pre_delay_samples < 0)
+        return alsep_fail(ctx, ALSEP_ERR_ARG, "alsep_reverb_apply: bad argument");
+    const int k = ola_block_log2(n_ir, log2_block);
+    if (k < 0)
+        return alsep_fail(ctx, ALSEP_ERR_ARG, "alsep_reverb_apply: impulse response of %lld taps (1 .. %lld) or block exponent %d (2^k >= 2 taps, k <= 21)",
+                          (long long)n_ir, (long long)kMaxIrTaps, log2_block);
+    const float *dry_end = dry + ((int64_t)(channels - 1) * ld + n), *out_end = out + ((int64_t)(channels - 1) * ld_out + n);
+    if (dry < out_end && out < dry_end) return alsep_fail(ctx, ALSEP_ERR_ARG, "alsep_reverb_apply: out overlaps dry");
+    const int64_t F = (int64_t)1 << k, L = n_ir, S = F - L + 1;
+    const int64_t fit = ws_bytes / ((int64_t)sizeof(cplx) << k);            // F-point buffers the workspace holds
+    if (fit < 3) return alsep_fail(ctx, ALSEP_ERR_ARG, "alsep_reverb_apply: workspace too small");
+    const int64_t head = pre_delay_samples < n ? pre_delay_samples : n;
+    const int64_t n_blocks = ceil_div64(n - head, S);                       // convolution samples 0 .. n - pre are all that survive the crop
+    int64_t per_batch = (fit - 1) / 2;
+    if (per_batch > n_blocks) per_batch = n_blocks;
+    if (head > 0) {
+        hipLaunchKernelGGL(ola_head_kernel, dim3(rv_grid(channels * head)), dim3(kRvThreads), 0, ctx->stream, dry, out, channels, ld, ld_out, head);
+        ALSEP_LAUNCH_CHECK(ctx, "ola_head_kernel");
+    }
+    if (n_blocks == 0) return ALSEP_OK;
+    cplx* h = (cplx*)ws;
+    cplx* a = h + F;
+    cplx* b = a + per_batch * F;
+    // the IR's spectrum, once per call; the ping-pong starts in the buffer that makes the last pass land in h
+    const int passes = (k + 2) / 3;
+    cplx* h0 = passes % 2 == 0 ? h : a;
+    hipLaunchKernelGGL(ir_pad_kernel, dim3(rv_grid(F)), dim3(kRvThreads), 0, ctx->stream, ir, L, 1.0 / (double)F, h0, F);
+    ALSEP_LAUNCH_CHECK(ctx, "ir_pad_kernel");
+    cplx* hs = nullptr;
+    if (int rc = fft_pow2(ctx, h0, h0 == h ? a : h, k, -1.0, &hs)) return rc;
+    if (hs != h) return alsep_fail(ctx, ALSEP_ERR_STATE, "alsep_reverb_apply: spectrum landed in the wrong buffer");
+    for (int c = 0; c < channels; c += 2) {
+        const float* x0 = dry + (int64_t)c * ld;
+        const float* x1 = c + 1 < channels ? x0 + ld : nullptr;
+        float* y0 = out + (int64_t)c * ld_out;
+        float* y1 = x1 ? y0 + ld_out : nullptr;
+        for (int64_t b0 = 0; b0 < n_blocks; b0 += per_batch) {
+            const int64_t nb = n_blocks - b0 < per_batch ? n_blocks - b0 : per_batch;
+            hipLaunchKernelGGL(ola_gather_kernel, dim3(rv_grid(nb * F)), dim3(kRvThreads), 0, ctx->stream, x0, x1, n, a, k, S, L, b0, nb);
+            ALSEP_LAUNCH_CHECK(ctx, "ola_gather_kernel");
+            cplx *f = nullptr, *y = nullptr;
+            if (int rc = fft_pow2_batched(ctx, a, b, k, -1.0, nb, &f)) return rc;
+            hipLaunchKernelGGL(ola_product_kernel, dim3(rv_grid(nb * F)), dim3(kRvThreads), 0, ctx->stream, f, h, k, nb);
+            ALSEP_LAUNCH_CHECK(ctx, "ola_product_kernel");
+            if (int rc = fft_pow2_batched(ctx, f, f == a ? b : a, k, +1.0, nb, &y)) return rc;
+            hipLaunchKernelGGL(ola_finish_kernel, dim3(rv_grid(nb * S)), dim3(kRvThreads), 0, ctx->stream, y, x0, x1, y0, y1, n, k, S, L,
+                               pre_delay_samples, wet_gain, b0, nb);
+            ALSEP_LAUNCH_CHECK(ctx, "ola_finish_kernel");
+        }
+    }
     return ALSEP_OK;
 }
 

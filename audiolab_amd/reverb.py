@@ -14,12 +14,22 @@ Reference behaviours kept (oracle/reverb_oracle.py lists them; pinned by tests/g
 ``max(argmax - (len(dry) - 1), 0)`` of a correlation stored in circular order, i.e. 0 for realistic inputs; an odd-length wet signal
 yields n - 1 samples.  One reference behaviour NOT kept: with numpy >= 2 (the reference pins 2.0.2) its ``json.dump`` raises on the
 np.float32 ratios and leaves a truncated file behind (the call site logs "Error extracting IR"); this build writes the values.
+
+``apply_reverb`` (:179-209) is the consumer of that file -- wrappers/merge.py:7,118 puts the room back on a processed vocal stem with it:
+``clip(dry + 0.7 * pad(fftconvolve(dry_c, ir, "full"), (pre_delay_samples, 0))[:len(dry)], -1, 1)`` per channel.  Here the convolution is
+overlap-save in double precision on the device (``alsep_reverb_apply``: blocks of 2^k >= 2 len(ir) points, two channels per complex
+transform, a bounded workspace whatever the track length); ``apply_reverb_array`` is the entry point for stems already in device memory.
+Kept: the pre-delay is ``int(params["pre_delay"] * sr)`` with the DRY file's rate (:187), whatever ``params["sample_rate"]`` says (a
+WARNING is logged when they differ); a negative one raises ValueError as ``np.pad`` does (:197); the 0.7 wet gain and the clip (:205-206);
+a ``.wav`` output is 16-bit PCM, ``sf.write``'s default for that extension (:208).  The reference's float32 transform of the dry signal
+(scipy.fft keeps single precision) is not reproduced: this result is the exact convolution rounded to float32.
 """
 from __future__ import annotations
 
 import ctypes as C
 import json
 import logging
+import os
 from typing import Optional, Tuple, Union
 
 import numpy as np
@@ -147,3 +157,74 @@ def extract_reverb(dry_path: Audio, wet_path: Audio, param_output_path: str, wie
         json.dump(params, f, indent=2)
     logger.info(f"Extracted parameters saved: {param_output_path}")
     return param_output_path
+
+
+# ---- apply_reverb (:179-209) --------------------------------------------------------------------------------------------------------
+WET_GAIN = 0.7                                                               # :205
+MAX_WORKSPACE_BYTES = 1 << 30                                                # default batch: as many blocks as fit in 1 GiB
+
+
+def load_params_from_file(param_path: str) -> dict:
+    """handlers/reverb.py:44-46"""
+    with open(param_path, "r") as file:
+        return json.load(file)
+
+
+def apply_reverb_array(dry, ir, pre_delay_samples: int, wet_gain: float = WET_GAIN, *, log2_block: int = 0, blocks_per_batch: int = 0,
+                       ctx: Optional[Context] = None) -> torch.Tensor:
+    """``clip(dry + wet_gain * pad(fftconvolve(dry_c, ir, "full"), (pre_delay_samples, 0))[:N], -1, 1)`` per channel (:192-206) as a
+    float32 ``[C, N]`` device tensor.  ``dry``: float32 ``[C, N]`` or ``[N]``, tensor or array, device or host; ``ir``: float64 taps.
+    ``log2_block`` forces the overlap-save block length (0: from len(ir)), ``blocks_per_batch`` the blocks transformed side by side
+    (0: what a 1 GiB workspace holds); neither changes the result's value, the second not a bit of it."""
+    ctx = ctx if ctx is not None else _lib.default_context(None)
+    pre = int(pre_delay_samples)
+    if pre < 0:
+        raise ValueError("apply_reverb: the pre-delay can't be negative")    # np.pad's ValueError (:197)
+    dry_t = torch.as_tensor(dry, dtype=torch.float32)
+    if dry_t.dim() == 1:
+        dry_t = dry_t[None]
+    if dry_t.dim() != 2 or dry_t.shape[1] < 1:
+        raise AlsepError("apply_reverb: signals are [channels, samples]")
+    dry_t = dry_t.to(ctx.device).contiguous()
+    ir_t = torch.as_tensor(ir, dtype=torch.float64).reshape(-1).to(ctx.device).contiguous()
+    n_ir, (c, n) = ir_t.numel(), dry_t.shape
+    k = int(ctx.lib.alsep_reverb_apply_block_log2(n_ir, log2_block))
+    if k < 0:
+        raise AlsepError(f"apply_reverb: an impulse response of {n_ir} taps with block exponent {log2_block} is not supported "
+                         f"(1 .. 2^20 taps, 2^k >= 2 taps)")
+    n_blocks = max(1, -(-(n - min(pre, n)) // ((1 << k) - n_ir + 1)))
+    if blocks_per_batch <= 0:
+        blocks_per_batch = max(1, (MAX_WORKSPACE_BYTES // (16 << k) - 1) // 2)
+    need = int(ctx.lib.alsep_reverb_apply_workspace_bytes(n_ir, k, min(int(blocks_per_batch), n_blocks)))
+    ws = ctx.empty((need,), torch.uint8)
+    out = ctx.empty((c, n), torch.float32)
+    ctx.check(ctx.lib.alsep_reverb_apply(ctx.handle, _lib.ptr(dry_t), c, n, n, _lib.ptr(ir_t), n_ir, pre, float(wet_gain), k, _lib.ptr(out), n,
+                                         _lib.ptr(ws), need), "alsep_reverb_apply")
+    return out
+
+
+def apply_reverb(dry_path: Audio, param_path: Union[str, dict], output_path: str, sr: Optional[int] = None, ctx: Optional[Context] = None,
+                 subtype: str = "PCM_16") -> str:
+    """handlers/reverb.py:179-209.  ``dry_path``: a WAV path, or an in-memory signal with ``sr=``; ``param_path``: the JSON file
+    ``extract_reverb`` wrote, or its dictionary.  Writes ``output_path`` (16-bit PCM as ``sf.write`` does for a .wav path, :208;
+    ``subtype="FLOAT"`` for float32) and returns it."""
+    ctx = ctx if ctx is not None else _lib.default_context(None)
+    dry_t, sr = _load(dry_path, ctx, sr)
+    params = param_path if isinstance(param_path, dict) else load_params_from_file(param_path)
+    impulse_response = np.array(params["impulse_response"], dtype=np.float64)                # :186
+    pre_delay_samples = int(params["pre_delay"] * sr)                                        # :187 -- the dry file's rate
+    if "sample_rate" in params and params["sample_rate"] != sr:
+        logger.warning(f"apply_reverb: the impulse response was extracted at {params['sample_rate']} Hz, the dry signal has {sr} Hz; "
+                       f"applied sample by sample as the reference does")
+    final = apply_reverb_array(dry_t, impulse_response, pre_delay_samples, WET_GAIN, ctx=ctx)
+    wavio.write_wav(output_path, final.cpu().numpy(), sr, subtype=subtype)
+    return output_path
+
+
+def process_song(dry_path: str, wet_path: str, output_dir: str, ctx: Optional[Context] = None) -> str:
+    """handlers/reverb.py:216-226"""
+    param_file = os.path.join(output_dir, "reverb_params.json")
+    output_file = os.path.join(output_dir, "reverb_applied.wav")
+    extract_reverb(dry_path, wet_path, param_file, ctx=ctx)
+    apply_reverb(dry_path, param_file, output_file, ctx=ctx)
+    return output_file

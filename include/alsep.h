@@ -507,6 +507,18 @@ int alsep_rfft_mag_f64(alsep_ctx* ctx, const double* x, int64_t n, void* ws, int
 int64_t alsep_dft_f64_workspace_bytes(int64_t n);
 int alsep_dft_f64(alsep_ctx* ctx, const double* in, double* out, int64_t n, int inverse, void* ws, int64_t ws_bytes);
 
+/* ---- convolution reverb: replaces apply_reverb of handlers/reverb.py:179-209 (called from wrappers/merge.py:118 with the
+ * impulse_response.ir file that extract_reverb stored).  out[c] = clip(dry[c] + wet_gain * wet[c], -1, 1) with
+ * wet[c] = np.pad(fftconvolve(dry[c], ir, "full"), (pre_delay_samples, 0))[:n], float32 [channels][n] tensors with row strides ld /
+ * ld_out, ir: n_ir float64 taps on the device (1 .. 2^20).  Overlap-save in double precision on blocks of F = 2^k >= 2 n_ir points
+ * (log2_block = k, or 0: max(ceil(log2(2 n_ir)), 10)), two channels per complex transform.  The workspace holds the IR's spectrum and two
+ * F-point buffers per block of a batch: ws_bytes decides how many blocks run side by side (at least one), the result does not depend on
+ * it.  out must not overlap dry.  ALSEP_ERR_ARG: n_ir above the cap, a block too short for it, a negative pre-delay. */
+int alsep_reverb_apply_block_log2(int64_t n_ir, int log2_block);              /* k, or -1 for a bad geometry */
+int64_t alsep_reverb_apply_workspace_bytes(int64_t n_ir, int log2_block, int blocks_per_batch);   /* -1 for a bad geometry */
+int alsep_reverb_apply(alsep_ctx* ctx, const float* dry, int channels, int64_t n, int64_t ld, const double* ir, int64_t n_ir,
+                       int64_t pre_delay_samples, double wet_gain, int log2_block, float* out, int64_t ld_out, void* ws, int64_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif
