@@ -47,6 +47,13 @@ class TensorEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
 
+MIX_MAX_STEMS = 8          # ALSEP_MIX_MAX_STEMS
+
+
+class MixStem(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("n", C.c_int64), ("ld", C.c_int64), ("channels", C.c_int32), ("bits", C.c_int32)]
+
+
 _SIGNATURES = {
     "alsep_abi_version": (C.c_int, []),
     "alsep_experiments_enabled": (C.c_int, []),
@@ -187,6 +194,12 @@ _SIGNATURES = {
     "alsep_reverb_apply_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "alsep_reverb_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int,
                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "alsep_mix_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MixStem), C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
+                                C.c_void_p]),
+    "alsep_mix_power_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),
+    "alsep_mix_power": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_void_p, C.c_int64, C.c_void_p]),
+    "alsep_mix_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int64,
+                                   C.c_void_p, C.c_int64]),
     "alsep_nn_lstm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "alsep_nn_localstate_softmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]),
     "alsep_nn_blstm_unfold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int] * 5),

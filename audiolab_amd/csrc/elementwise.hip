@@ -482,3 +482,6 @@ extern "C" int alsep_zero_low_bins(alsep_ctx* ctx, void* spec, int dtype, int la
     ALSEP_LAUNCH_CHECK(ctx, "zero_low_bins_kernel");
     return ALSEP_OK;
 }
+
+// stem mixdown with loudness matching (the Merge wrapper): alsep_mix_sum / alsep_mix_power / alsep_mix_finish
+#include "mixdown.h"

@@ -14,8 +14,8 @@ WAVE_FORMAT_IEEE_FLOAT = 3
 WAVE_FORMAT_EXTENSIBLE = 0xFFFE
 
 
-def read_wav(path: str) -> Tuple[np.ndarray, int]:
-    """-> (audio [C, N] float32 in [-1, 1), sample_rate)."""
+def _chunks(path: str):
+    """-> ((format tag, channels, sample rate, bits), bytes of the data chunk)"""
     with open(path, "rb") as f:
         data = f.read()
     if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
@@ -40,6 +40,18 @@ def read_wav(path: str) -> Tuple[np.ndarray, int]:
         pos += 8 + size + (size & 1)
     if fmt is None or pcm is None:
         raise ValueError(f"{path}: missing fmt or data chunk")
+    return fmt, pcm
+
+
+def read_wav_info(path: str) -> Tuple[int, int, int, bool]:
+    """-> (channels, sample_rate, bits per sample, samples are IEEE floats)"""
+    (tag, ch, sr, bits), _ = _chunks(path)
+    return ch, sr, bits, tag == WAVE_FORMAT_IEEE_FLOAT
+
+
+def read_wav(path: str) -> Tuple[np.ndarray, int]:
+    """-> (audio [C, N] float32 in [-1, 1), sample_rate)."""
+    fmt, pcm = _chunks(path)
     tag, ch, sr, bits = fmt
     if tag == WAVE_FORMAT_IEEE_FLOAT and bits == 32:
         x = np.frombuffer(pcm, dtype="<f4").astype(np.float32)
@@ -63,7 +75,8 @@ def read_wav(path: str) -> Tuple[np.ndarray, int]:
 
 
 def write_wav(path: str, audio: np.ndarray, sr: int, subtype: str = "FLOAT") -> None:
-    """audio [C, N] (or [N]) -> WAV; subtype "FLOAT" (float32) or "PCM_16" (round-to-nearest, clipped)."""
+    """audio [C, N] (or [N]) -> WAV; subtype "FLOAT" (float32), "PCM_16" or "PCM_32" (round-to-nearest, clipped).  An integer array
+    under a PCM subtype holds the samples themselves (already on that grid): they are written as they are, clipped to the range."""
     a = np.asarray(audio)
     if a.ndim == 1:
         a = a[None, :]
@@ -72,9 +85,14 @@ def write_wav(path: str, audio: np.ndarray, sr: int, subtype: str = "FLOAT") -> 
     if subtype == "FLOAT":
         tag, bits = WAVE_FORMAT_IEEE_FLOAT, 32
         payload = inter.astype("<f4").tobytes()
-    elif subtype == "PCM_16":
-        tag, bits = WAVE_FORMAT_PCM, 16
-        payload = np.clip(np.rint(inter.astype(np.float64) * 32768.0), -32768, 32767).astype("<i2").tobytes()
+    elif subtype in ("PCM_16", "PCM_32"):
+        tag, bits = WAVE_FORMAT_PCM, int(subtype[4:])
+        full = float(1 << (bits - 1))
+        if np.issubdtype(inter.dtype, np.integer):
+            grid = np.clip(inter.astype(np.int64), -int(full), int(full) - 1)
+        else:
+            grid = np.clip(np.rint(inter.astype(np.float64) * full), -full, full - 1.0)
+        payload = grid.astype("<i2" if bits == 16 else "<i4").tobytes()
     else:
         raise ValueError(f"unsupported subtype {subtype}")
     block = ch * bits // 8

@@ -519,6 +519,33 @@ int64_t alsep_reverb_apply_workspace_bytes(int64_t n_ir, int log2_block, int blo
 int alsep_reverb_apply(alsep_ctx* ctx, const float* dry, int channels, int64_t n, int64_t ld, const double* ir, int64_t n_ir,
                        int64_t pre_delay_samples, double wet_gain, int log2_block, float* out, int64_t ld_out, void* ws, int64_t ws_bytes);
 
+/* ---- stem mixdown with loudness matching: replaces the pydub calls of wrappers/merge.py:15-45,146-151 (AudioSegment.overlay,
+ * effects.normalize, .dBFS, .apply_gain), i.e. audioop.add / max / rms / mul, on the signed integer grid of `bits` (16 or 32) with
+ * full scale M = 2^(bits-1).  The mix is int32 [channels][n] (row stride ld) for both widths; channels * n <= 2^31.
+ * 16-byte loads and stores are used on every operand whose rows start on 16-byte boundaries, scalar ones elsewhere. */
+#define ALSEP_MIX_MAX_STEMS 8
+typedef struct alsep_mix_stem {
+    const float* data;     /* device, float32 [channels][n], row stride ld */
+    int64_t n, ld;
+    int32_t channels;      /* that of the mix, or 1: feeds every channel */
+    int32_t bits;          /* source width b_s <= bits: the sample's grid value is q_{b_s}(x) << (bits - b_s),
+                            * q_b(x) = clip(rint(x 2^(b-1)), -2^(b-1), 2^(b-1) - 1), ties to even, NaN -> 0 */
+} alsep_mix_stem;
+/* acc = prev (or 0), then for each stem in order acc = clip(acc + v_k, -M, M - 1) (audioop.add saturates after every add) over the
+ * samples < min(n, n_k); *peak (device) = max|acc| of the result, |-M| = M included.  `stems` is a HOST array of n_stems <=
+ * ALSEP_MIX_MAX_STEMS entries; longer lists are chained through prev (which may be acc itself): the result does not depend on
+ * the split.  acc must not overlap a stem. */
+int alsep_mix_sum(alsep_ctx* ctx, const int32_t* prev, int64_t ld_prev, const alsep_mix_stem* stems, int n_stems, int channels, int64_t n,
+                  int bits, int32_t* acc, int64_t ld_acc, uint32_t* peak);
+/* y1 = floor(clip(acc f1, -M, M - 1)) (audioop.mul), not written: out (device) [0] = max|y1|, [1] / [2] = the sums of the high / low
+ * 32 bits of every y1^2, so that sum y1^2 = out[1] 2^32 + out[2] exactly.  Block partials in ws, finished by one block. */
+int64_t alsep_mix_power_workspace_bytes(int channels, int64_t n);
+int alsep_mix_power(alsep_ctx* ctx, const int32_t* acc, int channels, int64_t n, int64_t ld, int bits, double f1, void* ws, int64_t ws_bytes,
+                    uint64_t* out);
+/* out_i = floor(clip(y1 f2, -M, M - 1)) with y1 as above; out_f (optional, float32) = out_i / M.  out_i may be acc itself. */
+int alsep_mix_finish(alsep_ctx* ctx, const int32_t* acc, int channels, int64_t n, int64_t ld, int bits, double f1, double f2, int32_t* out_i,
+                     int64_t ld_i, float* out_f, int64_t ld_f);
+
 #ifdef __cplusplus
 }
 #endif
