@@ -2608,6 +2608,388 @@ us_stream_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf1
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// ds / us of the middle levels, pipelined across tiles (ALSEP_PIX_PIPE).  Same arithmetic as ds_split_stream_kernel and
+// us_stream_kernel -- the same weight fragments in registers, the same wave owns the same m-tiles (ds) or tap (us), every
+// accumulator runs over ks ascending, the same fp32 epilogue values and one rounding -- but the memory traffic of tile i + D
+// is requested before tile i is computed:
+//   * persistent workgroups of four waves, one per CU, striding statically over the tiles;
+//   * the activation tile (and, for us, the skip tile) comes into an LDS ring by LDS-DMA, D tiles ahead; the B fragments are
+//     ds_read_b128 from a swizzled image (LDS-DMA writes linearly, so the permutation is on the SOURCE address and on the
+//     read), once per wave from LDS instead of four times from L1;
+//   * one workgroup barrier per tile: behind it tile i's slot is complete, the slot of tile i - 1 is free for tile i + D, and
+//     the output image of tile i - 1 is complete -- it leaves as whole rows of 16-byte stores under tile i's MFMAs;
+//   * every wait in the tile loop is counted (vmcnt is in order: the stores issued behind an LDS-DMA are not waited for), and
+//     every LDS access in it is asm with our own lgkmcnt waits: a compiler-tracked LDS access would be given s_waitcnt vmcnt
+//     for ALL LDS-DMA in flight, i.e. drain the ring.
+// ------------------------------------------------------------------------------------------
+#ifdef ALSEP_CPU_EMUL
+static inline void lds_write_async_b64(bf16_t* lds_ptr, const bf16x4& v) { std::memcpy(lds_ptr, &v, 8); }
+template <int OFF>
+static inline void lds_read_async_f32x4(f32x4& dst, const float* lds_ptr) { std::memcpy(&dst, reinterpret_cast<const char*>(lds_ptr) + OFF, 16); }
+#else
+// lds_read_async_b128 for four floats
+template <int OFF>
+__device__ __forceinline__ void lds_read_async_f32x4(f32x4& dst, const float* lds_ptr) {
+    static_assert(OFF >= 0 && OFF < 65536 && OFF % 16 == 0, "ds offset field");
+    const unsigned addr = (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void*)lds_ptr;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
+}
+// 8-byte LDS write invisible to hipcc's waitcnt bookkeeping (completed by the lgkmcnt(0) of barrier_nodrain / lds_wait_n<0>)
+__device__ __forceinline__ void lds_write_async_b64(bf16_t* lds_ptr, const bf16x4& v) {
+    const unsigned addr = (unsigned)(unsigned long long)(__attribute__((address_space(3))) void*)lds_ptr;
+    asm volatile("ds_write_b64 %0, %1" : : "v"(addr), "v"(v) : "memory");
+}
+#endif
+template <typename F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+// f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>): loop indices that instruction immediates need
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+    static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+// counted wait at the top of tile i of a workgroup's n tiles: DMA(i) has landed.  Behind DMA(i) this wave has issued, in
+// order, the DMAs of the next D - 1 tiles (ND each) and the stores of one earlier tile per iteration since (NS each, none
+// in iteration 0); without all D - 1 successors (the last tiles) everything is waited for.
+template <int D, int ND, int NS>
+__device__ __forceinline__ void pipe_wait_tile(int i, int n) {
+    static_assert(D >= 1 && D * NS + (D - 1) * ND < 64, "vmcnt is a 6-bit counter");
+    if (i + D - 1 < n) {
+        if (i > D) wait_vmcnt<D * NS + (D - 1) * ND>();
+        else wait_vmcnt<(D - 1) * ND>();
+    } else {
+        wait_vmcnt<0>();
+    }
+}
+
+// ds: tiles of PX output pixels of one row.  The input of a tile is two runs (dy = 0, 1) of PX * 2C contiguous channels; slot
+// image [dy][PX px][SR 16-byte groups], group g of pixel row r at position g ^ swz(r): conflict-free for the ds_read_b128
+// lane groups (16 pixels x 2 adjacent k-groups) at both pixel strides -- 24 groups (C = 96: 8 distinct rows mod 16 slots) and
+// 36 groups (C = 144: 4 distinct).  Output image [PX][M + 8] bf16, two of them.
+template <int C_, int PX_, int D_> struct DsPipeCfg {
+    typedef DsSplitCfg<C_> S;
+    static constexpr int C = C_, M = S::M, MT = S::MT, KS = S::KS, MTW = S::MTW, PX = PX_, NI = PX_ / 16, D = D_, NSLOT = D_ + 1;
+    static constexpr int SR = C_ / 4, HALF_G = PX * SR, TILE_G = 2 * HALF_G, ND = TILE_G / kThreads;
+    static constexpr int MS = M + 8, OUT_GW = PX * M / 8 / 4, NS = (OUT_GW + 63) / 64;
+    static constexpr size_t tile_bytes = (size_t)TILE_G * 16, img_bytes = (size_t)PX * MS * sizeof(bf16_t);
+    static constexpr size_t lds_bytes = NSLOT * tile_bytes + 2 * img_bytes;
+    __host__ __device__ static constexpr int swz(int row) { return SR % 8 == 0 ? (row & 7) : ((row >> 2) & 2); }
+    static_assert(PX % 16 == 0 && HALF_G % 64 == 0 && TILE_G % kThreads == 0 && KS % 2 == 0 && SR % 4 == 0 && (PX * M / 8) % 4 == 0,
+                  "ds pipe geometry");
+    static_assert(lds_bytes <= 160 * 1024 && tile_bytes < 65536, "LDS of a CU; ds offset field");
+};
+template <int C_, int PX_, int D_>
+__global__ void __launch_bounds__(kThreads, 1)
+ds_pipe_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf16_t* __restrict__ Wf,
+               const float* __restrict__ scale, const float* __restrict__ shift, int64_t npix, int Tp, int Fp) {
+    typedef DsPipeCfg<C_, PX_, D_> P;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, lq = lane >> 4;
+    char* ring = alsep_smem;
+    bf16_t* img = reinterpret_cast<bf16_t*>(alsep_smem + P::NSLOT * P::tile_bytes);
+    bf16x8 wf[P::MTW][P::KS];
+    f32x4 sc[P::MTW], sh[P::MTW];
+#pragma unroll
+    for (int j = 0; j < P::MTW; ++j) {
+        const int mt = wave + 4 * j;
+#pragma unroll
+        for (int ks = 0; ks < P::KS; ++ks)
+            wf[j][ks] = mt < P::MT ? *reinterpret_cast<const bf16x8*>(Wf + ((size_t)(mt * P::KS + ks) * 64 + lane) * 8) : bf16x8{};
+        sc[j] = mt < P::MT ? *reinterpret_cast<const f32x4*>(scale + mt * 16 + 4 * lq) : f32x4{0.f, 0.f, 0.f, 0.f};
+        sh[j] = mt < P::MT ? *reinterpret_cast<const f32x4*>(shift + mt * 16 + 4 * lq) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    // LDS-DMA duty of this wave: ND consecutive 1 KiB pieces of the slot; lane offsets from the tile's first input pixel
+    unsigned xoff[P::ND];
+#pragma unroll
+    for (int q = 0; q < P::ND; ++q) {
+        const int pg = (wave * P::ND + q) * 64 + lane;
+        const int dy = pg / P::HALF_G, row = (pg % P::HALF_G) / P::SR, gp = pg % P::SR;
+        xoff[q] = (unsigned)dy * (2u * (unsigned)Fp * P::C * (unsigned)sizeof(bf16_t)) + (unsigned)((row * P::SR + (gp ^ P::swz(row))) * 16);
+    }
+    // B fragment of k-step kk of either dy: pixel row l15 (+ 16 ni), group 4 kk + lq, at its swizzled position
+    unsigned bk[P::KS / 2];
+#pragma unroll
+    for (int kk = 0; kk < P::KS / 2; ++kk) bk[kk] = (unsigned)((l15 * P::SR + ((kk * 4 + lq) ^ P::swz(l15))) * 16);
+    // output: wave w copies groups [w, w + 1) * OUT_GW of the image's PX * M / 8
+    unsigned ioff[P::NS];
+#pragma unroll
+    for (int t = 0; t < P::NS; ++t) {
+        const int g = wave * P::OUT_GW + t * 64 + lane;
+        ioff[t] = (unsigned)(((g / (P::M / 8)) * P::MS + (g % (P::M / 8)) * 8) * (int)sizeof(bf16_t));
+    }
+
+    const int64_t ntile = npix / P::PX;                      // Fp % PX == 0: a tile is PX consecutive f' of one row
+    const int nmy = (int)((ntile - (int64_t)blockIdx.x + gridDim.x - 1) / gridDim.x);
+    auto issue = [&](int j) {
+        const int64_t p0 = ((int64_t)blockIdx.x + (int64_t)j * gridDim.x) * P::PX;
+        const int64_t fp0 = p0 % Fp, tp = (p0 / Fp) % Tp, bb = p0 / ((int64_t)Fp * Tp);
+        // input pixel (2tp + dy, 2(fp0 + j) + dx): k = (dy*2 + dx)*C + ci -> one run of PX * 2C per dy
+        const ALSEP_GLOBAL char* src = opaque_uniform_gptr(
+            reinterpret_cast<const char*>(X + ((bb * 2 * Tp + 2 * tp) * (2 * (int64_t)Fp) + 2 * fp0) * P::C));
+        char* dst = ring + (size_t)(j % P::NSLOT) * P::tile_bytes + (size_t)wave * (P::ND * 1024);
+#pragma unroll
+        for (int q = 0; q < P::ND; ++q) glds16_base(src, xoff[q], dst + q * 1024);
+    };
+    auto copy_out = [&](int j) {
+        const int64_t p0 = ((int64_t)blockIdx.x + (int64_t)j * gridDim.x) * P::PX;
+        ALSEP_GLOBAL char* yb = const_cast<ALSEP_GLOBAL char*>(
+            opaque_uniform_gptr(reinterpret_cast<const char*>(Y + p0 * P::M + (int64_t)wave * (P::OUT_GW * 8))));
+        const char* im = reinterpret_cast<const char*>(img) + (size_t)(j & 1) * P::img_bytes;
+        bf16x8 q[P::NS];
+#pragma unroll
+        for (int t = 0; t < P::NS; ++t)
+            if (t * 64 + lane < P::OUT_GW) lds_read_async_b128<0>(q[t], reinterpret_cast<const bf16_t*>(im + ioff[t]));
+        lds_wait_n<0>();
+#pragma unroll
+        for (int t = 0; t < P::NS; ++t)
+            if (t * 64 + lane < P::OUT_GW) stream_store(reinterpret_cast<ALSEP_GLOBAL bf16x8*>(yb + (unsigned)(t * 64 + lane) * 16u), q[t]);
+    };
+
+    wait_vmcnt<0>();                                         // weights, scale and shift are in registers
+#pragma unroll
+    for (int j = 0; j < P::D; ++j)
+        if (j < nmy) issue(j);
+    for (int i = 0; i < nmy; ++i) {
+        pipe_wait_tile<P::D, P::ND, P::NS>(i, nmy);
+        barrier_nodrain();                                   // tile i is in LDS for every wave; tile i - 1 is computed, its slot free
+        if (i + P::D < nmy) issue(i + P::D);
+        if (i > 0) copy_out(i - 1);
+        const bf16_t* slot = reinterpret_cast<const bf16_t*>(ring + (size_t)(i % P::NSLOT) * P::tile_bytes);
+        f32x4 acc[P::MTW][P::NI];
+#pragma unroll
+        for (int j = 0; j < P::MTW; ++j)
+#pragma unroll
+            for (int ni = 0; ni < P::NI; ++ni) acc[j][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+        bf16x8 xf[2][P::NI];
+        static_for<P::NI>([&](auto nic) {
+            constexpr int ni = decltype(nic)::value;
+            lds_read_async_b128<ni * 16 * P::SR * 16>(xf[0][ni], slot + bk[0] / sizeof(bf16_t));
+        });
+        static_for<P::KS>([&](auto ksc) {
+            constexpr int ks = decltype(ksc)::value, b = ks & 1;
+            if constexpr (ks + 1 < P::KS) {
+                constexpr int dy1 = (ks + 1) / (P::KS / 2), kk1 = (ks + 1) % (P::KS / 2);
+                static_for<P::NI>([&](auto nic) {
+                    constexpr int ni = decltype(nic)::value;
+                    lds_read_async_b128<dy1 * P::HALF_G * 16 + ni * 16 * P::SR * 16>(xf[1 - b][ni], slot + bk[kk1] / sizeof(bf16_t));
+                });
+                lds_wait_n<P::NI>();                         // step ks has landed, step ks + 1 is in flight
+            } else {
+                lds_wait_n<0>();
+            }
+#pragma unroll
+            for (int j = 0; j < P::MTW; ++j)
+                if (wave + 4 * j < P::MT) {                  // wave-uniform
+#pragma unroll
+                    for (int ni = 0; ni < P::NI; ++ni) mma_step(acc[j][ni], wf[j][ks], xf[b][ni]);
+                }
+        });
+        bf16_t* im = img + (size_t)(i & 1) * (P::PX * P::MS);
+#pragma unroll
+        for (int j = 0; j < P::MTW; ++j) {
+            const int mt = wave + 4 * j;
+            if (mt < P::MT) {
+#pragma unroll
+                for (int ni = 0; ni < P::NI; ++ni) {
+                    bf16x4 q;                                // one rounding, as store4
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) q[r] = (bf16_t)fmaxf(fmaf(acc[j][ni][r], sc[j][r], sh[j][r]), 0.f);
+                    lds_write_async_b64(im + (ni * 16 + l15) * P::MS + mt * 16 + 4 * lq, q);
+                }
+            }
+        }
+    }
+    barrier_nodrain();
+    copy_out(nmy - 1);
+}
+
+// us: tiles of PX input pixels of one row.  X slot: wave w's quarter of the pixel rows (PX / 4 rows of SRX 16-byte groups, padded
+// to whole 1 KiB pieces: the surplus lanes re-read the quarter's last group into the pad) at w * XREG; group g of row r at
+// g ^ swz(r) (24 groups: 8 distinct rows mod 16 slots; 18 groups are conflict-free as they are).  S slot: the skip tile
+// [dy][2 PX output pixels][NG groups], group g of pixel p at position (g + rot(p)) mod NG, so that the eight-byte accesses of the
+// MFMA lanes (16 pixels 2 C2 elements apart) spread over the banks.  The epilogue multiplies there: lane (tap, pixel, 4 channels)
+// reads its skip values, forms relu(bn(acc)) * skip in fp32 -- the product us_stream_kernel forms in its copy-out -- rounds once
+// and writes the result over them, so the slot becomes the output image and leaves by the addresses it came from.
+template <int CIN, int C2_, int NI_, int D_> struct UsPipeCfg {
+    typedef UsCfg<CIN, C2_, NI_> U;
+    static constexpr int C = CIN, C2 = C2_, NI = NI_, PX = 16 * NI_, MT = U::MT, KS = U::KS, D = D_, NSX = D_ + 1, NSS = D_ + 2;
+    static constexpr int SRX = CIN / 8, XW_G = (PX / 4) * SRX, NDX = (XW_G + 63) / 64, XREG = NDX * 1024;
+    static constexpr int NG = C2_ / 8, ROW_G = 2 * PX * NG, S_G = 2 * ROW_G, NDS = S_G / kThreads;
+    static constexpr int ND = NDX + NDS, NS = NDS;
+    static constexpr size_t x_bytes = 4 * (size_t)XREG, s_bytes = (size_t)S_G * 16, bn_bytes = 2 * (size_t)C2_ * sizeof(float);
+    static constexpr size_t lds_bytes = NSX * x_bytes + NSS * s_bytes + bn_bytes;
+    __host__ __device__ static constexpr int swz(int row) { return SRX % 8 == 0 ? (row & 7) : 0; }
+    __host__ __device__ static constexpr int rot(int px) { return NG % 4 == 0 ? ((px >> 2) & 7) : ((px >> 3) & 3); }
+    static_assert(PX % 32 == 0 && ROW_G % 64 == 0 && S_G % kThreads == 0 && (NG % 4 == 0 ? NG >= 8 : NG >= 4), "us pipe geometry");
+    static_assert(lds_bytes <= 160 * 1024 && x_bytes < 65536 && s_bytes < 65536, "LDS of a CU; ds offset field");
+};
+template <int CIN, int C2_, int NI_, int D_>
+__global__ void __launch_bounds__(kThreads, 1)
+us_pipe_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf16_t* __restrict__ Wf,
+               const float* __restrict__ scale, const float* __restrict__ shift, const bf16_t* __restrict__ skip,
+               int64_t npix, int Tp, int Fp) {
+    typedef UsPipeCfg<CIN, C2_, NI_, D_> P;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, lq = lane >> 4;
+    const int dy = wave >> 1, dx = wave & 1;
+    char* xring = alsep_smem;
+    char* sring = alsep_smem + P::NSX * P::x_bytes;
+    float* bn = reinterpret_cast<float*>(alsep_smem + P::NSX * P::x_bytes + P::NSS * P::s_bytes);   // [scale | shift][C2]
+    bf16x8 wf[P::MT][P::KS];
+#pragma unroll
+    for (int mt = 0; mt < P::MT; ++mt)
+#pragma unroll
+        for (int ks = 0; ks < P::KS; ++ks)
+            wf[mt][ks] = *reinterpret_cast<const bf16x8*>(Wf + ((size_t)((wave * P::MT + mt) * P::KS + ks) * 64 + lane) * 8);
+    for (int c = tid; c < 2 * P::C2; c += kThreads) bn[c] = c < P::C2 ? scale[c] : shift[c - P::C2];
+    // LDS-DMA duty of this wave: its quarter of the X rows, and NDS consecutive 1 KiB pieces of the S slot
+    unsigned xoff[P::NDX], soff[P::NDS];
+#pragma unroll
+    for (int q = 0; q < P::NDX; ++q) {
+        const int gi = q * 64 + lane < P::XW_G ? q * 64 + lane : P::XW_G - 1;
+        const int row = gi / P::SRX, gp = gi % P::SRX;
+        xoff[q] = (unsigned)(((wave * (P::PX / 4) + row) * P::SRX + (gp ^ P::swz(row))) * 16);
+    }
+#pragma unroll
+    for (int q = 0; q < P::NDS; ++q) {
+        const int pg = (wave * P::NDS + q) * 64 + lane;
+        const int row = pg / P::ROW_G, px = (pg % P::ROW_G) / P::NG, gp = pg % P::NG;
+        soff[q] = (unsigned)row * (2u * (unsigned)Fp * P::C2 * (unsigned)sizeof(bf16_t)) + (unsigned)((px * P::NG + (gp - P::rot(px) + P::NG) % P::NG) * 16);
+    }
+    // B fragment of k-step ks: pixel row l15 (+ 16 ni), group 4 ks + lq at its swizzled position.  CIN % 32 != 0: the last step's
+    // groups beyond CIN (zero weights) read a valid group and are zeroed.
+    unsigned bk[P::KS];
+#pragma unroll
+    for (int ks = 0; ks < P::KS; ++ks) {
+        const int g = ks * 4 + lq < P::SRX ? ks * 4 + lq : P::SRX - 1;
+        bk[ks] = (unsigned)((l15 >> 3) * P::XREG + ((l15 & 7) * P::SRX + (g ^ P::swz(l15 & 7))) * 16);
+    }
+    const bool klast_ok = P::C % 32 == 0 || (P::KS - 1) * 4 + lq < P::SRX;
+    // epilogue: output pixel 2 (16 ni + l15) + dx of row dy, channels 16 mt + 4 lq ..: half (lq & 1) of group 2 mt + (lq >> 1)
+    const int opx = 2 * l15 + dx;
+    const unsigned ebase = (unsigned)((dy * P::ROW_G + opx * P::NG) * 16);
+    const int erot = (lq >> 1) + P::rot(opx);
+
+    const int64_t ntile = npix / P::PX;                      // Fp % PX == 0: a tile is PX consecutive f' of one row
+    const int nmy = (int)((ntile - (int64_t)blockIdx.x + gridDim.x - 1) / gridDim.x);
+    auto out_base = [&](int j) {
+        const int64_t p0 = ((int64_t)blockIdx.x + (int64_t)j * gridDim.x) * P::PX;
+        const int64_t fp0 = p0 % Fp, tp = (p0 / Fp) % Tp, bb = p0 / ((int64_t)Fp * Tp);
+        return ((bb * 2 * Tp + 2 * tp) * (2 * (int64_t)Fp) + 2 * fp0) * P::C2;
+    };
+    auto issue = [&](int j) {
+        const int64_t p0 = ((int64_t)blockIdx.x + (int64_t)j * gridDim.x) * P::PX;
+        const ALSEP_GLOBAL char* xs = opaque_uniform_gptr(reinterpret_cast<const char*>(X + p0 * P::C));
+        const ALSEP_GLOBAL char* ss = opaque_uniform_gptr(reinterpret_cast<const char*>(skip + out_base(j)));
+        char* xd = xring + (size_t)(j % P::NSX) * P::x_bytes + (size_t)wave * P::XREG;
+        char* sd = sring + (size_t)(j % P::NSS) * P::s_bytes + (size_t)wave * (P::NDS * 1024);
+#pragma unroll
+        for (int q = 0; q < P::NDX; ++q) glds16_base(xs, xoff[q], xd + q * 1024);
+#pragma unroll
+        for (int q = 0; q < P::NDS; ++q) glds16_base(ss, soff[q], sd + q * 1024);
+    };
+    auto copy_out = [&](int j) {
+        ALSEP_GLOBAL char* yb = const_cast<ALSEP_GLOBAL char*>(opaque_uniform_gptr(reinterpret_cast<const char*>(Y + out_base(j))));
+        const bf16_t* sd = reinterpret_cast<const bf16_t*>(sring + (size_t)(j % P::NSS) * P::s_bytes + (size_t)wave * (P::NDS * 1024)) + lane * 8;
+        bf16x8 q[P::NDS];
+        static_for<P::NDS>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            lds_read_async_b128<t * 1024>(q[t], sd);
+        });
+        lds_wait_n<0>();
+#pragma unroll
+        for (int t = 0; t < P::NDS; ++t) stream_store(reinterpret_cast<ALSEP_GLOBAL bf16x8*>(yb + soff[t]), q[t]);
+    };
+
+    wait_vmcnt<0>();                                         // weights are in registers
+#pragma unroll
+    for (int j = 0; j < P::D; ++j)
+        if (j < nmy) issue(j);
+    for (int i = 0; i < nmy; ++i) {
+        pipe_wait_tile<P::D, P::ND, P::NS>(i, nmy);
+        barrier_nodrain();               // tile i (X, skip) is in LDS for every wave (first tile: bn too); tile i - 1 is an output image
+        if (i + P::D < nmy) issue(i + P::D);
+        if (i > 0) copy_out(i - 1);
+        const bf16_t* xs = reinterpret_cast<const bf16_t*>(xring + (size_t)(i % P::NSX) * P::x_bytes);
+        f32x4 acc[P::MT][P::NI];
+#pragma unroll
+        for (int mt = 0; mt < P::MT; ++mt)
+#pragma unroll
+            for (int ni = 0; ni < P::NI; ++ni) acc[mt][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+        bf16x8 xf[2][P::NI];
+        static_for<P::NI>([&](auto nic) {
+            constexpr int ni = decltype(nic)::value;
+            lds_read_async_b128<ni * 2 * P::XREG>(xf[0][ni], xs + bk[0] / sizeof(bf16_t));
+        });
+        static_for<P::KS>([&](auto ksc) {
+            constexpr int ks = decltype(ksc)::value, b = ks & 1;
+            if constexpr (ks + 1 < P::KS) {
+                static_for<P::NI>([&](auto nic) {
+                    constexpr int ni = decltype(nic)::value;
+                    lds_read_async_b128<ni * 2 * P::XREG>(xf[1 - b][ni], xs + bk[ks + 1] / sizeof(bf16_t));
+                });
+                lds_wait_n<P::NI>();                         // step ks has landed, step ks + 1 is in flight
+            } else {
+                lds_wait_n<0>();
+                if (P::C % 32 != 0) {
+#pragma unroll
+                    for (int ni = 0; ni < P::NI; ++ni) xf[b][ni] = klast_ok ? xf[b][ni] : bf16x8{};
+                }
+            }
+#pragma unroll
+            for (int mt = 0; mt < P::MT; ++mt)
+#pragma unroll
+                for (int ni = 0; ni < P::NI; ++ni) mma_step(acc[mt][ni], wf[mt][ks], xf[b][ni]);
+        });
+        // relu(bn(.)) * skip in fp32, one rounding, over the skip values; m-tile mt + 1's operands are requested under mt's arithmetic
+        bf16_t* sl = reinterpret_cast<bf16_t*>(sring + (size_t)(i % P::NSS) * P::s_bytes + ebase);
+        const float* bnl = bn + 4 * lq;
+        auto eoff = [&](int mt) {                            // group (2 mt + (lq >> 1) + rot) mod NG of this lane's pixel, in elements
+            int t = 2 * mt + erot;
+            t = t >= P::NG ? t - P::NG : t;
+            return t * 8;
+        };
+        bf16x8 ev[2][P::NI];
+        f32x4 scv[2], shv[2];
+        auto eread = [&](auto mtc) {
+            constexpr int mt = decltype(mtc)::value, eb = mt & 1;
+            const bf16_t* p = sl + eoff(mt);
+            static_for<P::NI>([&](auto nic) {
+                constexpr int ni = decltype(nic)::value;
+                lds_read_async_b128<ni * 32 * P::NG * 16>(ev[eb][ni], p);
+            });
+            lds_read_async_f32x4<0>(scv[eb], bnl + mt * 16);
+            lds_read_async_f32x4<P::C2 * 4>(shv[eb], bnl + mt * 16);
+        };
+        eread(std::integral_constant<int, 0>{});
+        static_for<P::MT>([&](auto mtc) {
+            constexpr int mt = decltype(mtc)::value, b = mt & 1;
+            if constexpr (mt + 1 < P::MT) {
+                eread(std::integral_constant<int, mt + 1>{});
+                lds_wait_n<P::NI + 2>();
+            } else {
+                lds_wait_n<0>();
+            }
+            bf16_t* p = sl + eoff(mt) + (lq & 1) * 4;
+            static_for<P::NI>([&](auto nic) {
+                constexpr int ni = decltype(nic)::value;
+                const bf16x4 sk = (lq & 1) ? __builtin_shufflevector(ev[b][ni], ev[b][ni], 4, 5, 6, 7)
+                                           : __builtin_shufflevector(ev[b][ni], ev[b][ni], 0, 1, 2, 3);
+                bf16x4 q;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) q[r] = (bf16_t)(fmaxf(fmaf(acc[mt][ni][r], scv[b][r], shv[b][r]), 0.f) * (float)sk[r]);
+                lds_write_async_b64(p + ni * 32 * P::NG * 8, q);
+            });
+        });
+    }
+    barrier_nodrain();
+    copy_out(nmy - 1);
+}
+
 #ifndef ALSEP_F16_TU
 #include "tdfnet_f32s.h"     // float32 storage with split-half contractions (the float32 network lives in the main translation unit)
 #endif
@@ -3553,11 +3935,62 @@ int pix_stream_enabled() {
     static const int v = [] { const char* e = getenv("ALSEP_PIX_STREAM"); return e ? atoi(e) : 1; }();
     return v;
 }
+// ALSEP_PIX_PIPE: 1 (default) = the ds / us of the middle levels run on ds_pipe_kernel / us_pipe_kernel for the instances in
+// kPixPipeRouted (each is routed there only where it measured faster than its stream kernel on the same box:
+// profiles/pix_pipe_kernel_stats.txt); 0 = never (the stream kernels, as before); 2 = every instance (measurements, tests).
+// ALSEP_PIX_PIPE_GRID=n caps their grid (tests: several tiles per workgroup at small shapes).
+enum { kPixPipeDs96 = 1, kPixPipeDs144 = 2, kPixPipeUs192 = 4, kPixPipeUs144 = 8 };
+constexpr int kPixPipeRouted = kPixPipeDs96 | kPixPipeDs144 | kPixPipeUs192 | kPixPipeUs144;
+bool pix_pipe_routed(int kind) {
+    static const int v = [] { const char* e = getenv("ALSEP_PIX_PIPE"); return e ? atoi(e) : 1; }();
+    return v >= 2 || (v == 1 && (kPixPipeRouted & kind));
+}
+unsigned pix_pipe_grid(alsep_ctx* ctx, int64_t ntile) {     // more than 128 KiB of LDS: one workgroup per CU
+    static const int cap = [] { const char* e = getenv("ALSEP_PIX_PIPE_GRID"); return e ? atoi(e) : 0; }();
+    int64_t grid = device_cu_count(ctx);
+    if (cap > 0 && cap < grid) grid = cap;
+    return (unsigned)std::min<int64_t>(grid, ntile);
+}
+template <int C_, int PX_, int D_>
+hipError_t launch_ds_pipe(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t* Y, int64_t ncols, int Tp, int Fp) {
+    typedef DsPipeCfg<C_, PX_, D_> P;
+    const hipError_t e = hipFuncSetAttribute((const void*)ds_pipe_kernel<C_, PX_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P::lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ds_pipe_kernel<C_, PX_, D_>), dim3(pix_pipe_grid(ctx, ncols / P::PX)), dim3(kThreads), P::lds_bytes, ctx->stream, X, Y,
+                       (const bf16_t*)L.wfrag.p, (const float*)L.scale.p, (const float*)L.shift.p, ncols, Tp, Fp);
+    return hipSuccess;
+}
+template <int CIN, int C2_, int NI_, int D_>
+hipError_t launch_us_pipe(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* skip, int64_t ncols, int Tp, int Fp) {
+    typedef UsPipeCfg<CIN, C2_, NI_, D_> P;
+    const hipError_t e = hipFuncSetAttribute((const void*)us_pipe_kernel<CIN, C2_, NI_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P::lds_bytes);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((us_pipe_kernel<CIN, C2_, NI_, D_>), dim3(pix_pipe_grid(ctx, ncols / P::PX)), dim3(kThreads), P::lds_bytes, ctx->stream, X, Y,
+                       (const bf16_t*)L.wfrag.p, (const float*)L.scale.p, (const float*)L.shift.p, skip, ncols, Tp, Fp);
+    return hipSuccess;
+}
 int run_pix_stream(alsep_ctx* ctx, int mode, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* skip, int64_t ncols,
                    int Tp, int Fp) {
     ProfScope prof(ctx, ALSEP_PROF_PIX);
     const int64_t ntile = ncols / 64;
-    if (mode == PIX_DS && L.M == Ds48::M) {
+    // the pipelined kernels: one more launch-count name each, the pinned names below are noted as before
+    if (mode == PIX_DS && L.M == DsSplitCfg<96>::M && pix_pipe_routed(kPixPipeDs96)) {
+        ALSEP_HIP(ctx, (launch_ds_pipe<96, 64, 1>(ctx, L, X, Y, ncols, Tp, Fp)));
+        note_launch(ctx, "ds_pipe_kernel<96>");
+        note_launch(ctx, "ds_split_stream_kernel<96>");
+    } else if (mode == PIX_DS && L.M == DsSplitCfg<144>::M && pix_pipe_routed(kPixPipeDs144)) {
+        ALSEP_HIP(ctx, (launch_ds_pipe<144, 32, 2>(ctx, L, X, Y, ncols, Tp, Fp)));
+        note_launch(ctx, "ds_pipe_kernel<144>");
+        note_launch(ctx, "ds_split_stream_kernel<144>");
+    } else if (mode != PIX_DS && L.K == 192 && pix_pipe_routed(kPixPipeUs192)) {
+        ALSEP_HIP(ctx, (launch_us_pipe<192, 144, 2, 1>(ctx, L, X, Y, skip, ncols, Tp, Fp)));
+        note_launch(ctx, "us_pipe_kernel<192,144>");
+        note_launch(ctx, "us_stream_kernel<192,144>");
+    } else if (mode != PIX_DS && L.K == 144 && pix_pipe_routed(kPixPipeUs144)) {
+        ALSEP_HIP(ctx, (launch_us_pipe<144, 96, 2, 2>(ctx, L, X, Y, skip, ncols, Tp, Fp)));
+        note_launch(ctx, "us_pipe_kernel<144,96>");
+        note_launch(ctx, "us_stream_kernel<144,96>");
+    } else if (mode == PIX_DS && L.M == Ds48::M) {
         const size_t lds = 4 * 64 * Ds48::MS * sizeof(bf16_t);
         const int64_t gx = std::min<int64_t>(ceil_div64(ntile, 4), 256);
         hipLaunchKernelGGL(ds48_stream_kernel, dim3((unsigned)gx), dim3(kThreads), lds, ctx->stream, X, Y, (const bf16_t*)L.wfrag.p,
