@@ -54,6 +54,12 @@ class MixStem(C.Structure):
     _fields_ = [("data", C.c_void_p), ("n", C.c_int64), ("ld", C.c_int64), ("channels", C.c_int32), ("bits", C.c_int32)]
 
 
+class MixOperand(C.Structure):
+    """alsep_mix_operand: a float32 stem or the int32 running mix, with the sample rates it is brought from and to (0, 0: as it is)"""
+    _fields_ = [("data", C.c_void_p), ("n", C.c_int64), ("ld", C.c_int64), ("in_rate", C.c_int64), ("out_rate", C.c_int64),
+                ("channels", C.c_int32), ("bits", C.c_int32), ("is_mix", C.c_int32)]
+
+
 _SIGNATURES = {
     "alsep_abi_version": (C.c_int, []),
     "alsep_experiments_enabled": (C.c_int, []),
@@ -200,6 +206,8 @@ _SIGNATURES = {
     "alsep_mix_power": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_void_p, C.c_int64, C.c_void_p]),
     "alsep_mix_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int64,
                                    C.c_void_p, C.c_int64]),
+    "alsep_mix_ratecv_length": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64]),
+    "alsep_mix_sum_rates": (C.c_int, [C.c_void_p, C.POINTER(MixOperand), C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "alsep_nn_lstm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "alsep_nn_localstate_softmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64]),
     "alsep_nn_blstm_unfold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int] * 5),

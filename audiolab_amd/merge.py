@@ -19,9 +19,18 @@ Host maths, in Python floats (pydub's ``normalize(headroom=0.1)`` and ``normaliz
     if prevent_clipping: gain = min(gain, -20 * math.log10(peak1 / M))   # peak1 = max|y1|
     f2   = db_to_float(gain)                                             # target -inf -> f2 = 0 -> zeros
 
+Stems of differing sample rates.  ``AudioSegment.overlay`` first brings both segments to the larger frame rate (``_sync`` ->
+``set_frame_rate`` -> ``audioop.ratecv(data, width, channels, rate, new_rate, None)``: linear interpolation on 32-bit values, truncated toward
+zero), before the sample widths meet.  With R the running rate of the mix: a stem below R is resampled on its own width's grid and then
+shifted up; a stem above R has the running mix -- the saturated sum so far -- resampled on the grid of the widest stem in it, the mix takes
+the new length and R becomes the stem's rate; the file is written at the final R.  ``alsep_mix_sum_rates`` (the fourth pass of
+csrc/mixdown.h) does the interpolation inside the sum; every rise of R is a launch boundary (``plan_rates``).  The ``ratecv`` arithmetic is
+pinned by tests/golden/merge_rates.npz (scripts/make_golden_merge_rates.py).  ``merge_files(mixed_rates="ratecv")`` switches it on; the
+default, ``"error"``, raises as before.
+
 Departures from the reference: lengths are sample-exact (pydub slices by milliseconds); float samples reach the integer grid by
-``clip(rint(x 2^(b-1)))`` on the stem's own width b (the reference's conversion goes through ffmpeg); stems with differing sample rates are
-an error (pydub would ``audioop.ratecv`` them).
+``clip(rint(x 2^(b-1)))`` on the stem's own width b (the reference's conversion goes through ffmpeg); the width of the mix is fixed from the
+start (pydub widens it when a wider stem arrives); ``ratecv``'s filter weights and state, which pydub never passes, are not built.
 """
 from __future__ import annotations
 
@@ -49,6 +58,7 @@ class MixRecord:
     gain_dB: float
     f2: float
     bits: int = 32
+    rate: int = 0              # the sample rate of the mix: the largest one given (0: no rates were given)
 
     def as_dict(self) -> dict:
         return asdict(self)
@@ -151,6 +161,118 @@ def mix_finish(ctx: Context, acc: torch.Tensor, bits: int, f1: float, f2: float,
     return (out_i, out_f) if want_float else out_i
 
 
+# ---- stems of differing sample rates ----------------------------------------------------------------------------------------------------
+RATE_MAX = 1 << 20                                                           # of a rate divided by the pair's gcd
+
+
+def ratecv_length(n: int, in_rate: int, out_rate: int) -> int:
+    """samples ``audioop.ratecv`` returns for ``n`` input samples: floor((n - 1) outr / inr) + 1 on the reduced pair"""
+    n, in_rate, out_rate = int(n), int(in_rate), int(out_rate)
+    if n < 1 or in_rate < 1 or out_rate < 1:
+        raise AlsepError(f"ratecv: {n} samples from rate {in_rate} to {out_rate}")
+    g = math.gcd(in_rate, out_rate)
+    inr, outr = in_rate // g, out_rate // g
+    if inr > RATE_MAX or outr > RATE_MAX:
+        raise AlsepError(f"ratecv: the rates {in_rate} -> {out_rate} reduce to {inr} -> {outr}, above {RATE_MAX}")
+    return (n - 1) * outr // inr + 1
+
+
+@dataclass
+class RateLaunch:
+    """one launch of the resampling sum pass"""
+    mix: Optional[Tuple[int, int]]                       # None: no mix yet; (R, R): the mix as it is; (R, R'): the mix resampled
+    mix_width: int                                       # the grid the mix is resampled on: the widest stem in it
+    stems: List[Tuple[int, Optional[Tuple[int, int]]]]   # (index of the stem, its rate pair or None)
+    rate: int                                            # the running rate R after this launch
+    length: Optional[int] = None                         # samples per row of the mix after this launch (when the first length was given)
+
+
+def plan_rates(rates: Sequence[int], widths: Sequence[int], max_per_launch: int = 0, n: Optional[int] = None) -> List[RateLaunch]:
+    """Host only.  The launches that mix stems of the given rates and source widths in pydub's order: the running rate R starts as the first
+    stem's; a stem below R carries the pair (its rate, R); a stem above R starts a new launch whose first operand is the mix carrying
+    (R, its rate) -- every earlier add has to be complete before the mix is resampled -- and R becomes its rate.  No launch holds more
+    than ``max_per_launch`` stems (0: as many as one holds), nor more than ALSEP_MIX_MAX_STEMS operands with the mix."""
+    rates, widths = [int(r) for r in rates], [int(w) for w in widths]
+    if not rates or len(rates) != len(widths):
+        raise AlsepError("plan_rates: one rate and one width per stem, at least one stem")
+    if any(r < 1 for r in rates):
+        raise AlsepError(f"plan_rates: sample rates are positive, got {rates}")
+    per = _lib.MIX_MAX_STEMS if max_per_launch <= 0 else min(int(max_per_launch), _lib.MIX_MAX_STEMS)
+    rate, length = rates[0], n
+    launches: List[RateLaunch] = []
+    cur = RateLaunch(None, 0, [], rate, length)
+    for k, r in enumerate(rates):
+        if r > rate:
+            if cur.stems or cur.mix is not None:
+                launches.append(cur)
+            length = None if length is None else ratecv_length(length, rate, r)
+            cur = RateLaunch((rate, r), max(widths[:k]), [], r, length)
+            rate = r
+        elif len(cur.stems) >= min(per, _lib.MIX_MAX_STEMS - (cur.mix is not None)):
+            launches.append(cur)
+            cur = RateLaunch((rate, rate), max(widths[:k]), [], rate, length)
+        cur.stems.append((k, (r, rate) if r < rate else None))
+    launches.append(cur)
+    return launches
+
+
+def _mix_sum_rates(ctx: Context, operands, channels: int, n_out: int, bits: int, acc: torch.Tensor, peak: torch.Tensor) -> None:
+    arr = (_lib.MixOperand * len(operands))(*operands)
+    p, _, _, ld = _rows(acc, "mix_sum_rates")
+    ctx.check(ctx.lib.alsep_mix_sum_rates(ctx.handle, arr, len(operands), channels, n_out, bits, p, ld, _lib.ptr(peak)), "alsep_mix_sum_rates")
+
+
+def mix_sum_rates(ctx: Context, stems: Sequence[torch.Tensor], widths: Sequence[int], rates: Sequence[int], bits: int,
+                  max_per_launch: int = 0) -> Tuple[torch.Tensor, int, int]:
+    """``mix_sum`` for stems of differing sample rates -> (int32 mix [C, N] at the largest rate, max|mix|, that rate)"""
+    if not stems or len(stems) != len(widths) or len(stems) != len(rates):
+        raise AlsepError("mix_sum_rates: one width and one rate per stem, at least one stem")
+    c = max(s.shape[0] for s in stems)
+    peak = ctx.empty((1,), torch.int32)
+    acc = None
+    for launch in plan_rates(rates, widths, max_per_launch, stems[0].shape[1]):
+        operands = []
+        if launch.mix is not None:
+            p, _, n, ld = _rows(acc, "mix_sum_rates")
+            resampled = launch.mix[0] != launch.mix[1]
+            operands.append(_lib.MixOperand(p, n, ld, launch.mix[0], launch.mix[1], c, launch.mix_width if resampled else bits, 1))
+            if resampled:                                                    # a resampled mix must not be acc itself
+                old, acc = acc, empty_mix(ctx, c, launch.length)             # noqa: F841 (the operand, alive until the launch is queued)
+        else:
+            acc = empty_mix(ctx, c, launch.length)
+        for k, pair in launch.stems:
+            s = stems[k]
+            if s.dtype != torch.float32:
+                raise AlsepError("mix_sum_rates: stems are float32")
+            p, ck, nk, ld = _rows(s, f"mix_sum_rates: stem {k}")
+            if ck not in (1, c):
+                raise AlsepError(f"mix_sum_rates: stem {k} has {ck} channels, the mix {c}")
+            operands.append(_lib.MixOperand(p, nk, ld, pair[0] if pair else 0, pair[1] if pair else 0, ck, int(widths[k]), 0))
+        _mix_sum_rates(ctx, operands, c, launch.length, bits, acc, peak)
+        rate = launch.rate
+    return acc, int(peak.item()) & 0xFFFFFFFF, rate
+
+
+def ratecv_array(x, in_rate: int, out_rate: int, width: int, ctx: Optional[Context] = None) -> torch.Tensor:
+    """``audioop.ratecv(x, width // 8, channels, in_rate, out_rate, None)`` -> int32 [C, K] on the grid of ``width`` (16 or 32), K =
+    ``ratecv_length``.  ``x`` [C, N]: float32, quantised on that grid first, or int32 samples already on it."""
+    ctx = ctx if ctx is not None else _lib.default_context(None)
+    t = torch.as_tensor(x)
+    is_int = t.dtype == torch.int32
+    if not is_int:
+        t = t.to(torch.float32)
+    if t.dim() == 1:
+        t = t[None]
+    t = t.to(ctx.device).contiguous()
+    p, c, n, ld = _rows(t, "ratecv_array")
+    if width not in (16, 32):
+        raise AlsepError(f"ratecv_array: width {width}, expected 16 or 32")
+    k = ratecv_length(n, in_rate, out_rate)
+    out, peak = empty_mix(ctx, c, k), ctx.empty((1,), torch.int32)
+    _mix_sum_rates(ctx, [_lib.MixOperand(p, n, ld, int(in_rate), int(out_rate), c, int(width), 1 if is_int else 0)], c, k, int(width), out, peak)
+    return out
+
+
 # ---- mixdown ------------------------------------------------------------------------------------------------------------------------
 def _as_stem(ctx: Context, x) -> torch.Tensor:
     t = torch.as_tensor(x, dtype=torch.float32)
@@ -176,7 +298,7 @@ def source_dbfs(source, ctx: Optional[Context] = None, bits: int = 32) -> float:
 
 
 def mixdown_array(stems, source, prevent_clipping: bool = True, bits: Optional[int] = None, src_bits: Optional[Sequence[int]] = None,
-                  max_per_launch: int = 0, ctx: Optional[Context] = None) -> Tuple[torch.Tensor, MixRecord]:
+                  max_per_launch: int = 0, ctx: Optional[Context] = None, rates: Optional[Sequence[int]] = None) -> Tuple[torch.Tensor, MixRecord]:
     """Mix ``stems`` (float32 [C_k, N_k], device or host; the first one sets the length, a 1-channel stem feeds every channel) and match the
     loudness of ``source``: a float32 [C, N] signal, a ``(signal, width)`` pair when the source is a 16-bit file, or the target dBFS itself.
     ``src_bits``: the source width of every stem (default: ``bits``, or 32); ``bits``: the width of the mix, by default 16 iff every stem's
@@ -201,24 +323,37 @@ def mixdown_array(stems, source, prevent_clipping: bool = True, bits: Optional[i
         target = source_dbfs(source[0], ctx, int(source[1]))
     else:
         target = source_dbfs(source, ctx)
-    acc, peak = mix_sum(ctx, stems, src_bits, bits, max_per_launch)
+    rate = 0
+    if rates is not None:
+        rates = [int(r) for r in rates]
+        if len(rates) != len(stems):
+            raise AlsepError("mixdown: one sample rate per stem")
+        rate = max(rates)
+    if rates is not None and len(set(rates)) > 1:
+        acc, peak, rate = mix_sum_rates(ctx, stems, src_bits, rates, bits, max_per_launch)
+    else:
+        acc, peak = mix_sum(ctx, stems, src_bits, bits, max_per_launch)
     if peak == 0:
-        return acc, MixRecord(0, 1.0, 0, -math.inf, target, 0.0, 1.0, bits)
+        return acc, MixRecord(0, 1.0, 0, -math.inf, target, 0.0, 1.0, bits, rate)
     f1 = normalize_factor(peak, bits)
     peak1, s = mix_power(ctx, acc, bits, f1)
     rms = rms_of(s, acc.shape[0] * acc.shape[1])
     current, gain, f2 = match_gain(target, rms, peak1, bits, prevent_clipping)
     out = mix_finish(ctx, acc, bits, f1, f2)
-    return out, MixRecord(peak, f1, rms, current, target, gain, f2, bits)
+    return out, MixRecord(peak, f1, rms, current, target, gain, f2, bits, rate)
 
 
 StemInput = Union[str, Tuple[torch.Tensor, int, int]]
 
 
 def merge_files(paths: Sequence[StemInput], src_file: str, out_path: str, prevent_clipping: bool = True, bits: Optional[int] = None,
-                max_per_launch: int = 0, ctx: Optional[Context] = None) -> MixRecord:
+                max_per_launch: int = 0, ctx: Optional[Context] = None, mixed_rates: str = "error") -> MixRecord:
     """``paths``: WAV files, or ``(device signal [C, N], sample rate, width)`` for a stem that is already in device memory; ``src_file``: the
-    WAV whose loudness the mix is brought to.  Writes ``out_path`` as PCM_16 or PCM_32 according to the width of the mix."""
+    WAV whose loudness the mix is brought to.  Writes ``out_path`` as PCM_16 or PCM_32 according to the width of the mix.  ``mixed_rates``:
+    what to do with stems of differing sample rates -- ``"error"``: ValueError; ``"ratecv"``: resample as pydub's overlay does and write the
+    file at the largest rate."""
+    if mixed_rates not in ("error", "ratecv"):
+        raise ValueError(f"merge: mixed_rates is 'error' or 'ratecv', not {mixed_rates!r}")
     ctx = ctx if ctx is not None else _lib.default_context(None)
     stems: List[torch.Tensor] = []
     widths: List[int] = []
@@ -233,13 +368,14 @@ def merge_files(paths: Sequence[StemInput], src_file: str, out_path: str, preven
             stems.append(t)
         widths.append(grid_of(width))
         rates.append(int(sr))
-    if len(set(rates)) > 1:
-        raise ValueError(f"merge: the stems have different sample rates {sorted(set(rates))}; resampling them (audioop.ratecv in pydub) is not "
-                         f"built")
+    if len(set(rates)) > 1 and mixed_rates == "error":
+        raise ValueError(f"merge: the stems have different sample rates {sorted(set(rates))}; mixed_rates='ratecv' resamples them as pydub "
+                         f"does (audioop.ratecv)")
     src_audio, _ = wavio.read_wav(src_file)
     src_width = wavio.read_wav_info(src_file)[2]
     mix, rec = mixdown_array(stems, (torch.from_numpy(src_audio).to(ctx.device), src_width), prevent_clipping=prevent_clipping, bits=bits,
-                             src_bits=[min(w, bits) for w in widths] if bits else widths, max_per_launch=max_per_launch, ctx=ctx)
+                             src_bits=[min(w, bits) for w in widths] if bits else widths, max_per_launch=max_per_launch, ctx=ctx,
+                             rates=rates if len(set(rates)) > 1 else None)
     samples = mix.cpu().numpy()
-    wavio.write_wav(out_path, samples.astype(np.int16) if rec.bits == 16 else samples, rates[0], subtype="PCM_16" if rec.bits == 16 else "PCM_32")
+    wavio.write_wav(out_path, samples.astype(np.int16) if rec.bits == 16 else samples, rec.rate or rates[0], subtype="PCM_16" if rec.bits == 16 else "PCM_32")
     return rec

@@ -16,7 +16,10 @@ Departures from the reference:
   * a non-zero ``pitch_shift`` with a stem that is not a ``(Cloned)`` one raises NotImplementedError before any work: the reference shells
     out to ffmpeg's rubberband filter (util/audio_track.py), which is not built;
   * a ``src_file`` that is not a WAV goes through ``ensure_wav`` (one ffmpeg transcode) before its loudness is read;
-  * stems must share one sample rate (pydub would resample);
+  * stems of differing sample rates -- the default chain's case: Separate writes 44.1 kHz, a cloned voice comes at the model's 40 or
+    48 kHz -- raise ValueError while the class attribute ``mixed_rates`` is ``"error"``, the default; with ``Merge.mixed_rates = "ratecv"``
+    they are resampled on the GPU with the integer arithmetic of ``audioop.ratecv``, which pydub's overlay runs in the reference, and the
+    merged file is written at the largest rate (pydub's control flow around it is restated from its source, unpinned);
   * float samples reach the integer grid by ``clip(rint(x 2^(b-1)))``; the reference's conversion goes through ffmpeg;
   * recombining the merged audio with a video source (:162-185) is out of scope.
 """
@@ -72,6 +75,8 @@ class Merge(BaseWrapper):
 
     # an audiolab_amd._lib.Context to run on (None: the default context of the current device)
     ctx = None
+    # stems of differing sample rates: "error" (ValueError) or "ratecv" (resampled as pydub's overlay does); not a kwarg of the reference
+    mixed_rates = "error"
 
     def process_audio(self, pj_inputs: List[ProjectFiles], callback=None, **kwargs: Dict[str, Any]) -> List[ProjectFiles]:
         pj_outputs = []
@@ -113,7 +118,8 @@ class Merge(BaseWrapper):
                     os.remove(output_file)
 
                 record = merge.merge_files(new_inputs, ensure_wav(project.src_file), output_file,
-                                           prevent_clipping=filtered_kwargs.get("prevent_clipping", True), ctx=self.ctx)
+                                           prevent_clipping=filtered_kwargs.get("prevent_clipping", True), ctx=self.ctx,
+                                           mixed_rates=self.mixed_rates)
                 logger.info(f"Merged {len(new_inputs)} stems: {record.as_dict()}")
                 project.add_output("merged", output_file)
                 pj_outputs.append(project)

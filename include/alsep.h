@@ -546,6 +546,32 @@ int alsep_mix_power(alsep_ctx* ctx, const int32_t* acc, int channels, int64_t n,
 int alsep_mix_finish(alsep_ctx* ctx, const int32_t* acc, int channels, int64_t n, int64_t ld, int bits, double f1, double f2, int32_t* out_i,
                      int64_t ld_i, float* out_f, int64_t ld_f);
 
+/* ---- the sum pass for operands of differing sample rates: audioop.ratecv(data, width, channels, in_rate, out_rate, None) -- what
+ * pydub's AudioSegment.overlay reaches through _sync / set_frame_rate -- inside the sum.  With weightA = 1, weightB = 0 and no state the
+ * routine is linear interpolation on 32-bit values: both rates divided by their gcd give inr, outr (1 .. 2^20 each); for a sample u on
+ * the grid of width w (16 or 32) let x = u << (32 - w); output k of N inputs, k < K = floor((N - 1) outr / inr) + 1, is
+ *     j = ceil(k inr / outr), d = j outr - k inr, o = (int)(((double)x[j - 1] d + (double)x[j] (outr - d)) / outr), x[-1] = 0,
+ * truncated toward zero, and the result is o >> (32 - w) (arithmetic).  Channels are independent. */
+typedef struct alsep_mix_operand {
+    const void* data;      /* device: float32 [channels][n] (a stem) or int32 [channels][n] (the running mix, is_mix != 0), row stride ld */
+    int64_t n, ld;
+    int64_t in_rate, out_rate;   /* both 0, or equal: the operand is added as it is; else it is resampled from in_rate to out_rate */
+    int32_t channels;      /* that of the result, or 1 (stems only): feeds every channel */
+    int32_t bits;          /* a stem: its source width b_s as in alsep_mix_stem, resampled on that grid: ratecv_{b_s}(q_{b_s}(x)) << (bits - b_s);
+                            * the mix: the grid it is resampled on, ratecv_b(mix >> (bits - b)) << (bits - b) -- the width of the widest
+                            * stem in it.  16 or 32 wherever a rate pair is given */
+    int32_t is_mix;        /* only operand 0 may be the mix; without a rate pair it may be acc itself */
+} alsep_mix_operand;
+/* K above, n when the rates are equal; -1: n < 1 or > 2^31, a rate < 1, or a reduced rate above 2^20 */
+int64_t alsep_mix_ratecv_length(int64_t n, int64_t in_rate, int64_t out_rate);
+/* acc = 0, then for each operand in order acc = clip(acc + v_k, -M, M - 1) over the samples below min(n_out, the operand's length after
+ * resampling); *peak (device) = max|acc| as alsep_mix_sum.  `operands` is a HOST array of 1 .. ALSEP_MIX_MAX_STEMS entries.  Operand 0
+ * sets the length: n_out must equal its length after resampling.  A resampled operand must not overlap acc (a thread reads samples its
+ * neighbours write).  ALSEP_ERR_ARG before any launch for anything else: a rate < 1 beside a rate, a reduced rate above 2^20, a width
+ * other than 16 or 32 with a rate pair, channels * n_out > 2^31. */
+int alsep_mix_sum_rates(alsep_ctx* ctx, const alsep_mix_operand* operands, int n_operands, int channels, int64_t n_out, int bits,
+                        int32_t* acc, int64_t ld_acc, uint32_t* peak);
+
 #ifdef __cplusplus
 }
 #endif
