@@ -62,7 +62,6 @@ class MixOperand(C.Structure):
 
 _SIGNATURES = {
     "alsep_abi_version": (C.c_int, []),
-    "alsep_experiments_enabled": (C.c_int, []),
     "alsep_create": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "alsep_destroy": (C.c_int, [C.c_void_p]),
     "alsep_last_error": (C.c_char_p, [C.c_void_p]),

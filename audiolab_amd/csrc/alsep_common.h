@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
@@ -151,6 +152,13 @@ struct DeviceGuard {
     } while (0)
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// An integer switch from the environment: atoi of the variable, or dflt where it is not set.  Callers keep the value in a function-local
+// static (static const int v = env_int("ALSEP_X", 1);), so that a switch is read once per process.
+static inline int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 template <typename T> struct dtype_of;
 template <> struct dtype_of<float> { static constexpr int value = ALSEP_F32; };

@@ -105,9 +105,8 @@ __device__ __forceinline__ void lds_wait_n() {
 
 // no instruction may be scheduled across this point
 __device__ __forceinline__ void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
-// shader-clock counter (cycles) and the constant 100 MHz counter, for in-kernel phase stamps (timing experiments only)
+// shader-clock counter (cycles), for the in-kernel phase stamps of nn_gemm_h2_kernel's timing instance
 __device__ __forceinline__ unsigned long long clock_cycles() { return __builtin_amdgcn_s_memtime(); }
-__device__ __forceinline__ unsigned long long clock_100mhz() { return __builtin_amdgcn_s_memrealtime(); }
 
 // Extends the live range of a register value to this point (no code).
 // A per-lane integer the optimiser must treat as a NEW value from here on: values derived from it are recomputed after this point

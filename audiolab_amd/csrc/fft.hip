@@ -591,7 +591,7 @@ static int istft_pick_run(int n_blocks, int Q, int64_t n_chunks, int slots) {
 
 // ALSEP_STFT_R16=0 falls back to the generic multi-pass kernel for 4096 / 6144 (A/B timing, cross-check)
 static int stft_r16_enabled() {
-    static const int v = [] { const char* e = getenv("ALSEP_STFT_R16"); return e ? atoi(e) : 1; }();
+    static const int v = env_int("ALSEP_STFT_R16", 1);
     return v;
 }
 
@@ -717,14 +717,14 @@ static int launch_istft(alsep_ctx* ctx, const alsep_plan* p, const void* spec, i
     const int j_hi = (int)((keep_hi - 1 + N / 2) / p->hop) + 1;
     ProfScope prof(ctx, ALSEP_PROF_ISTFT);
     if constexpr (N == 4096 || N == 6144) {
-        static const int r16_on = [] { const char* e = getenv("ALSEP_ISTFT_R16"); return e ? atoi(e) : 1; }();
+        static const int r16_on = env_int("ALSEP_ISTFT_R16", 1);
         if (p->hop == 1024 && r16_on) {                      // production geometry: three-pass kernel
             constexpr int R2 = N / 256;
             const size_t lds_r = r16::istft_lds_bytes<R2>();
             const bool full = p->dim_f >= N / 2;                // production band: every bin below Nyquist is stored
             auto kern = full ? r16::istft_r16_kernel<R2, 8, InT, LAYOUT, true> : r16::istft_r16_kernel<R2, 8, InT, LAYOUT, false>;
             ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r));
-            static const int run_env = [] { const char* e = getenv("ALSEP_ISTFT_RUN"); return e ? atoi(e) : 0; }();
+            static const int run_env = env_int("ALSEP_ISTFT_RUN", 0);
             const int run = run_env > 0 ? run_env : istft_pick_run(j_hi - j_lo, Q, n_chunks, 3 * device_cu_count(ctx));
             const int groups_r = (j_hi - j_lo + run - 1) / run;
             for (int64_t b0 = 0; b0 < n_chunks; b0 += 32768) {
@@ -741,12 +741,12 @@ static int launch_istft(alsep_ctx* ctx, const alsep_plan* p, const void* spec, i
         }
     }
     if constexpr (N == 7680) {
-        static const int r30_on = [] { const char* e = getenv("ALSEP_ISTFT_R16"); return e ? atoi(e) : 1; }();
+        static const int r30_on = env_int("ALSEP_ISTFT_R16", 1);
         if (p->hop == 1024 && r30_on) {                      // the vocal models' geometry: three passes in the order 16, 16, 30
             const size_t lds_r = r16::istft_r30_lds_bytes();
             auto kern = r16::istft_r30_kernel<8, InT, LAYOUT>;
             ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r));
-            static const int run_env = [] { const char* e = getenv("ALSEP_ISTFT_RUN"); return e ? atoi(e) : 0; }();
+            static const int run_env = env_int("ALSEP_ISTFT_RUN", 0);
             const int run = run_env > 0 ? run_env : istft_pick_run(j_hi - j_lo, Q, n_chunks, 2 * device_cu_count(ctx));
             const int groups_r = (j_hi - j_lo + run - 1) / run;
             for (int64_t b0 = 0; b0 < n_chunks; b0 += 32768) {
@@ -766,7 +766,7 @@ static int launch_istft(alsep_ctx* ctx, const alsep_plan* p, const void* spec, i
             const size_t lds_r = sizeof(float2) * (size_t)N;
             ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)istft_regring_kernel<N, 1024, InT, LAYOUT>,
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r));
-            static const int run_env = [] { const char* e = getenv("ALSEP_ISTFT_RUN"); return e ? atoi(e) : 0; }();
+            static const int run_env = env_int("ALSEP_ISTFT_RUN", 0);
             const int run = run_env > 0 ? run_env : istft_pick_run(j_hi - j_lo, Q, n_chunks, 3 * device_cu_count(ctx));
             const int groups_r = (j_hi - j_lo + run - 1) / run;
             for (int64_t b0 = 0; b0 < n_chunks; b0 += 32768) {

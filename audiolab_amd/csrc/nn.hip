@@ -258,7 +258,7 @@ nn_gemm_tn_kernel(const float* __restrict__ A, const float* __restrict__ B, floa
 // 0: not applicable; 1: B [N][K] (K contiguous); 2: B [K][N] (N contiguous).  A is K-contiguous with 16-byte aligned rows that can
 // be read up to K rounded up to 4 (row stride >= that), likewise a K-contiguous B.
 static int gemm_tiled_mode(const float* A, const float* B, int M, int N, int K, const GemmStrides& a, const GemmStrides& b) {
-    static const int on = [] { const char* e = getenv("ALSEP_NN_GEMM_TN"); return e ? atoi(e) : 1; }();
+    static const int on = env_int("ALSEP_NN_GEMM_TN", 1);
     const int64_t k4 = (K + 3) / 4 * 4;
     if (!on || a.k != 1 || a.r % 4 || a.r < k4 || a.b1 % 4 || a.b2 % 4 || b.b1 % 4 || b.b2 % 4 || (((uintptr_t)A | (uintptr_t)B) & 15) ||
         (int64_t)M * N < 64 * 64 || K < 16)

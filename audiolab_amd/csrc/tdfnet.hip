@@ -269,6 +269,10 @@ conv3x3_bf16_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const 
                     const bf16_t* __restrict__ zero_page, int Th, int Fw, int Cin, int Cout, int tiles_t,
                     int tiles_f, int ntiles, int ablate, int stagger, int ny_fastest) {
     typedef ConvB16<TW> Cf;
+    // `ablate` (bit 0 no LDS-DMA, bit 1 no MFMA loop, bit 2 no stores) and `stagger` are the arguments of two finished timing experiments
+    // (profiles/r01_conv_ablation_*, r01_conv_stagger_experiment.txt); the library always passes 0.  They stay because the kernel
+    // compiled without them measured 1.2 % slower per launch at levels 3+ (profiles/conv_cleanup_ab.txt).  The cause was not looked for
+    // (only scalar control flow and moves differed: probably code layout); they can go once that is re-measured, e.g. with another compiler.
     // co-resident workgroups start together and would run their fill / MFMA / store phases in lockstep:
     // delay every other workgroup by about half a stage so that one fills while the other computes
     if (stagger > 0 && (blockIdx.x & 1))
@@ -366,7 +370,7 @@ conv3x3_bf16_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const 
 
 // ------------------------------------------------------------------------------------------
 // bf16 3x3 convolution, shallow levels (Cin = 48 or 96): persistent, weights in registers.
-// Measured on conv3x3_bf16_kernel (ALSEP_CONV_ABLATE): a workgroup's LDS fill, MFMA and store
+// Measured on conv3x3_bf16_kernel (profiles/r01_conv_ablation_*): a workgroup's LDS fill, MFMA and store
 // phases do not overlap (the two co-resident workgroups run in lockstep), and the fill is the
 // longest phase because every 256-pixel tile re-stages its 43 KiB weight block.  Here
 //  * a workgroup owns one 48-channel output block (ny = blockIdx.y) for its whole life and keeps
@@ -579,9 +583,6 @@ conv3x3_bf16_regw_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, c
 #undef ALSEP_RW_STAGE
 }
 
-#ifdef ALSEP_EXPERIMENTS   // conv3x3_bf16_pipe_kernel: superseded, kept for A/B runs and the emulation's bit-identity cross-checks
-#include "tdfnet_exp_pipe.inc"
-#endif
 // ------------------------------------------------------------------------------------------
 // bf16 3x3 convolution, levels >= 1 (Cout = 48*NY, NY = 2..4): big-tile persistent kernel.
 // The ablations (profiles/r01_conv_ablation_*) show the plain kernel bounded by what goes through
@@ -605,7 +606,7 @@ struct ConvBig {
     static constexpr int PINST = (PGROUPS + 63) / 64;       // 62
     static constexpr int WINST = WGROUPS / 64;              // 42: waves 0,1 issue 6, waves 2..7 issue 5
     static constexpr size_t ring_bytes = 16 * (size_t)(PGROUPS + 2 * WGROUPS);
-    static constexpr size_t lds_bytes = ring_bytes + 2 * NY * BN * sizeof(float) + 1024;   // + 1 KiB scratch (surplus DMA pieces)
+    static constexpr size_t lds_bytes = ring_bytes + 2 * NY * BN * sizeof(float);
     static_assert(lds_bytes <= 160 * 1024, "ConvBig: LDS budget");
     // Output-channel order of the packed weight rows.  An MFMA leaves a lane with rows 4 lq .. 4 lq + 3 of each 16-row block: with the
     // natural order that is 8 bytes of a pixel record per block and 24 (36) scattered 8-byte stores per tile and wave.  Here the 16-row
@@ -619,79 +620,13 @@ struct ConvBig {
     }
 };
 
-// ---- software-pipelined k-loop of the big-tile kernel (SWP) ------------------------------------------------------------
-// One k-step's fragments: 4 patch reads (pixel blocks ni at +ni*16*KC elements) and 3 weight reads (row blocks mi at
-// +mi*16*WGRP*8, k-step ST at +32*ST elements from the even / odd lane base), all with immediate offsets.
-template <typename Cf, int ST>
-__device__ __forceinline__ void big_issue_reads(bf16x8 (&xf)[4], bf16x8 (&wf)[3], const bf16_t* patch, const int (&pk)[Cf::NS],
-                                                const bf16_t* we, const bf16_t* wo) {
-    const bf16_t* pl = patch + pk[ST];
-    lds_read_async_b128<0 * 16 * Cf::KC * 2>(xf[0], pl);
-    lds_read_async_b128<1 * 16 * Cf::KC * 2>(xf[1], pl);
-    lds_read_async_b128<2 * 16 * Cf::KC * 2>(xf[2], pl);
-    lds_read_async_b128<3 * 16 * Cf::KC * 2>(xf[3], pl);
-    const bf16_t* wl = (ST & 1) ? wo : we;
-    lds_read_async_b128<(0 * 16 * Cf::WGRP * 8 + ST * 32) * 2>(wf[0], wl);
-    lds_read_async_b128<(1 * 16 * Cf::WGRP * 8 + ST * 32) * 2>(wf[1], wl);
-    lds_read_async_b128<(2 * 16 * Cf::WGRP * 8 + ST * 32) * 2>(wf[2], wl);
-}
-__device__ __forceinline__ void big_mma12(f32x4 (&acc)[3][4], const bf16x8 (&wf)[3], const bf16x8 (&xf)[4]) {
-#pragma unroll
-    for (int mi = 0; mi < 3; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) mma_step(acc[mi][ni], wf[mi], xf[ni]);
-}
-// steps ST (fragments in a) and ST + 1 (in b); on entry nothing of step ST has been requested when ST == 0, else a is in flight
-template <typename Cf, int ST, typename Dma>
-__device__ __forceinline__ void big_swp_steps(f32x4 (&acc)[3][4], bf16x8 (&xa)[4], bf16x8 (&wa)[3], bf16x8 (&xb)[4], bf16x8 (&wb)[3],
-                                              const bf16_t* patch, const int (&pk)[Cf::NS], const bf16_t* we, const bf16_t* wo,
-                                              Dma dma) {
-    if constexpr (ST < Cf::NS) {
-        if constexpr (ST == 0) big_issue_reads<Cf, 0>(xa, wa, patch, pk, we, wo);
-        big_issue_reads<Cf, ST + 1>(xb, wb, patch, pk, we, wo);
-        lds_wait_n<7>();                                     // a (the older 7 reads) has landed, b is in flight
-        big_mma12(acc, wa, xa);
-        if constexpr (ST < 6) dma(ST);
-        sched_fence();
-        if constexpr (ST + 2 < Cf::NS) {
-            big_issue_reads<Cf, ST + 2>(xa, wa, patch, pk, we, wo);
-            lds_wait_n<7>();
-        } else {
-            lds_wait_n<0>();
-        }
-        big_mma12(acc, wb, xb);
-        if constexpr (ST + 1 < 6) dma(ST + 1);
-        sched_fence();
-        big_swp_steps<Cf, ST + 2>(acc, xa, wa, xb, wb, patch, pk, we, wo, dma);
-    }
-}
-
-// STAMP (timing experiments, ALSEP_CONV_BIG_STAMP=1): per-wave cycle sums of the phases of a stage, written to `stamps`
-// [workgroup][wave][8] = {vmcnt wait, stage barrier, k-loop, patch barrier, patch issue, epilogue, whole kernel, 100 MHz ticks}
-// ABL (with STAMP only, wrong results): 1 no weight LDS-DMA in the k-loop, 2 one patch fragment read instead of four, 4 one weight
-// fragment read instead of three, 8 four MFMAs per k-step instead of twelve, 16 s_setprio 1 on waves 4-7, 32 no epilogue stores
-template <int NY, bool SWP = true, bool STAMP = false, int ABL = 0>   // SWP: software-pipelined k-loop (fragments of k-step s+1 requested before the MFMAs of s)
+template <int NY>
 __global__ void __launch_bounds__(kBigThreads, 2)
 conv3x3_bf16_big_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf16_t* __restrict__ Wp,
                         const float* __restrict__ scale, const float* __restrict__ shift,
                         const bf16_t* __restrict__ zero_page, int Th, int Fw, int Cin, int Cout, int tiles_t,
-                        int tiles_f, int ntiles, unsigned long long* __restrict__ stamps = nullptr) {
+                        int tiles_f, int ntiles) {
     typedef ConvBig<NY> Cf;
-    if constexpr ((ABL & 16) != 0) {
-        if (threadIdx.x >= 256) __builtin_amdgcn_s_setprio(1);
-    }
-    unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0}, tk0 = 0, tr0 = 0, tlast = 0;
-    auto stamp = [&](int k) {
-        if constexpr (STAMP) {
-            const unsigned long long now = clock_cycles();
-            tacc[k] += now - tlast;
-            tlast = now;
-        }
-    };
-    if constexpr (STAMP) {
-        tk0 = tlast = clock_cycles();
-        tr0 = clock_100mhz();
-    }
     bf16_t* patch = reinterpret_cast<bf16_t*>(alsep_smem);
     bf16_t* wring = patch + (size_t)Cf::PGROUPS * 8;
     float* ss = reinterpret_cast<float*>(alsep_smem + Cf::ring_bytes);
@@ -714,17 +649,6 @@ conv3x3_bf16_big_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, co
         const int tap = gc / Cf::CG, cg = gc % Cf::CG;
         return ((tap / 3) * Cf::PW + (tap % 3)) * Cf::KC + cg * 8;
     };
-    // SWP: per-lane LDS element offsets, computed once.  Patch: pixel (row = wave, col = l15) + k-group 4 st + lq.  Weights:
-    // (4 st + lq) ^ wswz = 4 (st ^ b) + c with b = wswz >> 2, c = lq ^ (wswz & 3): an even / odd k-step differs by +-32 elements
-    int pk[SWP ? Cf::NS : 1];
-    int wl_e = 0, wl_o = 0;
-    if constexpr (SWP) {
-#pragma unroll
-        for (int st = 0; st < Cf::NS; ++st) pk[st] = pbase[0] + koff_of(st);
-        const int b32 = (wswz >> 2) * 32, c8 = (lq ^ (wswz & 3)) * 8;
-        wl_e = l15 * Cf::WGRP * 8 + c8 + b32;
-        wl_o = l15 * Cf::WGRP * 8 + c8 - b32;
-    }
     const int my_tiles = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
     const int nstage = my_tiles * NY * nq;
 
@@ -778,17 +702,9 @@ conv3x3_bf16_big_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, co
         wsrc_next = Wp + ((int64_t)ny * nq + q) * (Cf::WGROUPS * 8);
         wdst_next = wring + (size_t)(s & 1) * Cf::WGROUPS * 8;
     };
-    bf16_t* const scratch = reinterpret_cast<bf16_t*>(alsep_smem + Cf::lds_bytes - 1024);   // SWP: landing place of the surplus DMAs
     auto weights_one = [&](int j) {
         const int i = wave + 8 * j;
-        if constexpr (SWP) {
-            // branch-free (a wave-uniform branch here splits the unrolled k-loop into basic blocks, and hipcc then waits
-            // lgkmcnt(0) at every join): waves 2..7 have no sixth piece and copy piece 0 into a 1 KiB scratch instead
-            const bool real = i < Cf::WINST;
-            glds16(wsrc_next + ((size_t)(real ? i : 0) * 64 + lane) * 8, real ? wdst_next + (size_t)i * 64 * 8 : scratch);
-        } else {
-            if (i < Cf::WINST) glds16(wsrc_next + ((size_t)i * 64 + lane) * 8, wdst_next + (size_t)i * 64 * 8);
-        }
+        if (i < Cf::WINST) glds16(wsrc_next + ((size_t)i * 64 + lane) * 8, wdst_next + (size_t)i * 64 * 8);
     };
 
     // Stage s: ny = s % NY, patch ps = s / NY (tile ps / nq, input chunk q = ps % nq).  In-order vmcnt bookkeeping:
@@ -812,10 +728,8 @@ conv3x3_bf16_big_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, co
         const bool after_epilogue = ny == 0 && q == 0 && s > 0;   // the previous stage ended a tile: its stores are younger
         if (after_epilogue) wait_vmcnt<ST>();
         else wait_vmcnt<0>();
-        stamp(0);
         barrier_nodrain();
-        stamp(1);
-        if (SWP || !last) weights_prep(s + 1);                   // SWP: the (branch-free) DMA of the last stage refills the free slot once more
+        if (!last) weights_prep(s + 1);
         {
             const bf16_t* wts = wring + (size_t)(s & 1) * Cf::WGROUPS * 8;
 #pragma unroll
@@ -827,43 +741,27 @@ conv3x3_bf16_big_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, co
 #pragma unroll
                             for (int ni = 0; ni < 4; ++ni) acc[yy][mi][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
                     }
-                    if constexpr (SWP) {
-                        // Fully unrolled, software-pipelined: the 7 fragment reads of k-step st + 1 are in flight while the 12 MFMAs
-                        // of st run.  Every LDS address is a per-lane base (pk[st]: patch, k-group 4 st + lq; we / wo: weight row l15,
-                        // swizzled group of an even / odd k-step) plus an instruction immediate, so a k-step costs no VALU (the rolled
-                        // loop recomputed the tap / group divisions per step: ~30 VALU instructions beside 12 MFMAs).  The reads are
-                        // asm (lds_read_async_b128) with our own counted waits: hipcc waits lgkmcnt(0) -- i.e. also for the reads it
-                        // has just issued -- at every second step of the same loop written with plain loads.
-                        const bf16_t* we = wts + wl_e;
-                        const bf16_t* wo = wts + wl_o;
-                        bf16x8 xa[4], wa[3], xb[4], wb[3];
-                        big_swp_steps<Cf, 0>(acc[yy], xa, wa, xb, wb, patch, pk, we, wo, [&](int j) { weights_one(j); });
-                    } else {
 #pragma unroll 2
                     for (int st = 0; st < Cf::NS; ++st) {
                         const int ko = koff_of(st);
                         bf16x8 xf[4], wf[3];
 #pragma unroll
-                        for (int ni = 0; ni < 4; ++ni) xf[ni] = (ABL & 2) && ni > 0 ? xf[0] : lds_frag<bf16_t>(patch + pbase[ni] + ko);
+                        for (int ni = 0; ni < 4; ++ni) xf[ni] = lds_frag<bf16_t>(patch + pbase[ni] + ko);
 #pragma unroll
                         for (int mi = 0; mi < 3; ++mi)
-                            wf[mi] = (ABL & 4) && mi > 0 ? wf[0] : lds_frag<bf16_t>(wts + ((mi * 16 + l15) * Cf::WGRP + ((4 * st + lq) ^ wswz)) * 8);
+                            wf[mi] = lds_frag<bf16_t>(wts + ((mi * 16 + l15) * Cf::WGRP + ((4 * st + lq) ^ wswz)) * 8);
 #pragma unroll
-                        for (int mi = 0; mi < ((ABL & 8) ? 1 : 3); ++mi)
+                        for (int mi = 0; mi < 3; ++mi)
 #pragma unroll
                             for (int ni = 0; ni < 4; ++ni) mma_step(acc[yy][mi][ni], wf[mi], xf[ni]);
-                        if (st < 6 && !last && !(ABL & 1)) weights_one(st);
-                    }
+                        if (st < 6 && !last) weights_one(st);
                     }
                 }
             }
         }
-        stamp(2);
         if (ny == NY - 1) {
             barrier_nodrain();                               // every wave has left the patch: it may be refilled
-            stamp(3);
             if (!last) issue_patch(ps + 1);
-            stamp(4);
             if (q == nq - 1) {
                 int t0, f0; int64_t b;
                 tile_coords(ps / nq, t0, f0, b);
@@ -883,7 +781,7 @@ conv3x3_bf16_big_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, co
 #pragma unroll
                             for (int r = 0; r < 4; ++r) y[4 * h + r] = fmaxf(fmaf(acc[bb / 3][bb % 3][ni][r], scv[r], shv[r]), 0.f);
                         }
-                        if constexpr (!(ABL & 32)) store8(yp + co, y);
+                        store8(yp + co, y);
                     }
                     if constexpr (Cf::NB % 2 == 1) {
                         constexpr int bb = Cf::NB - 1;
@@ -896,24 +794,11 @@ conv3x3_bf16_big_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, co
                         store4(yp + co, y);
                     }
                 }
-                stamp(5);
             }
-        }
-    }
-    if constexpr (SWP) wait_vmcnt<0>();                      // the surplus LDS-DMA of the last stage lands before the wave ends
-    if constexpr (STAMP) {
-        if (lane == 0 && stamps) {
-            unsigned long long* o = stamps + ((size_t)blockIdx.x * 8 + wave) * 8;
-            for (int k = 0; k < 6; ++k) o[k] = tacc[k];
-            o[6] = clock_cycles() - tk0;
-            o[7] = clock_100mhz() - tr0;
         }
     }
 }
 
-#ifdef ALSEP_EXPERIMENTS   // conv3x3_bf16_mny_kernel: superseded by conv3x3_bf16_mq_kernel, kept for A/B runs and the emulation
-#include "tdfnet_exp_mny.inc"
-#endif
 // ------------------------------------------------------------------------------------------
 // bf16 3x3 convolution, level 1 (c = 96): everything double-buffered.
 // Stamps of the merged kernel (profiles/r02_big_conv_stamps.txt): with its k-loop at 89 % of the MFMA issue floor, 17 % of the launch is
@@ -963,55 +848,33 @@ __device__ __forceinline__ void mq_mma(f32x4 (&acc)[6][4], const bf16x8 (&wf)[6]
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) mma_step(acc[b][ni], wf[b], xf[ni]);
 }
-// PRIO: a wave's issue priority falls as it advances through a stage (3, 2, 1, 0, 0): of the two waves of a SIMD the one that is behind
-// wins the arbitration, so they alternate k-step by k-step instead of the older one running ahead and the younger one finishing alone
-// with its stalls exposed (in-kernel stamps: k-loops of 2,970 / 4,780 cycles per stage for waves 0-3 / 4-7)
-template <int PRIO, int STL>
-__device__ __forceinline__ void mq_prio() {
-    if constexpr (PRIO != 0) __builtin_amdgcn_s_setprio(STL < 3 ? 3 - STL : 0);
-}
-template <int PT, int STL, int PRIO, typename Dma>
+template <int PT, int STL, typename Dma>
 __device__ __forceinline__ void mq_steps(f32x4 (&acc)[6][4], bf16x8 (&xa)[4], bf16x8 (&wa)[6], bf16x8 (&xb)[4], bf16x8 (&wb)[6],
                                          const bf16_t* patch, const int (&pk)[9], const bf16_t* wl, Dma dma) {
     constexpr int N = ConvMq::ksteps_of_part(PT), T0 = PT * ConvMq::KS;
     if constexpr (STL < N) {
         if constexpr (STL == 0) mq_issue_reads<T0, 0>(xa, wa, patch, pk, wl);
-        mq_prio<PRIO, STL>();
         lds_wait_n<0>();
         if constexpr (STL + 1 < N) mq_issue_reads<T0 + STL + 1, STL + 1>(xb, wb, patch, pk, wl);
         mq_mma(acc, wa, xa);
         dma(STL);
         sched_fence();
         if constexpr (STL + 1 < N) {
-            mq_prio<PRIO, STL + 1>();
             lds_wait_n<0>();
             if constexpr (STL + 2 < N) mq_issue_reads<T0 + STL + 2, STL + 2>(xa, wa, patch, pk, wl);
             mq_mma(acc, wb, xb);
             dma(STL + 1);
             sched_fence();
-            mq_steps<PT, STL + 2, PRIO>(acc, xa, wa, xb, wb, patch, pk, wl, dma);
+            mq_steps<PT, STL + 2>(acc, xa, wa, xb, wb, patch, pk, wl, dma);
         }
     }
 }
 
-template <bool STAMP = false, int PRIO = 0>
 __global__ void __launch_bounds__(kBigThreads, 2)
 conv3x3_bf16_mq_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf16_t* __restrict__ Wp, const float* __restrict__ scale,
                        const float* __restrict__ shift, const bf16_t* __restrict__ zero_page, int Th, int Fw, int Cin, int Cout, int tiles_t,
-                       int tiles_f, int ntiles, unsigned long long* __restrict__ stamps = nullptr) {
+                       int tiles_f, int ntiles) {
     typedef ConvMq Cf;
-    unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0}, tk0 = 0, tr0 = 0, tlast = 0;
-    auto stamp = [&](int k) {
-        if constexpr (STAMP) {
-            const unsigned long long now = clock_cycles();
-            tacc[k] += now - tlast;
-            tlast = now;
-        }
-    };
-    if constexpr (STAMP) {
-        tk0 = tlast = clock_cycles();
-        tr0 = clock_100mhz();
-    }
     bf16_t* const patch0 = reinterpret_cast<bf16_t*>(alsep_smem);
     bf16_t* const wring = patch0 + (size_t)2 * Cf::PBUF * 8;
     float* ss = reinterpret_cast<float*>(alsep_smem + Cf::ring_bytes);
@@ -1106,9 +969,7 @@ conv3x3_bf16_mq_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, con
         if (pt == 1) wait_vmcnt<Cf::PJ>();
         else if (q == 0 && s > 0) wait_vmcnt<ST>();
         else wait_vmcnt<0>();
-        stamp(0);
         barrier_nodrain();
-        stamp(1);
         weights_prep(s + 1);
         if (pt == 0) patch_prep(ps + 1);
         if (q == 0 && pt == 0) {
@@ -1127,7 +988,7 @@ conv3x3_bf16_mq_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, con
                     // LDS-DMA schedule.  Part 0 (5 taps): the next weight slot first, then the WHOLE next patch (not needed before
                     // the stage after next: still in flight at the next stage's vmcnt(PJ)); part 1 (4 taps): only its weights, early
                     if (k == 0)
-                        mq_steps<0, 0, PRIO>(acc, xa, wa, xb, wb, patch, pk, wl, [&](int st) {
+                        mq_steps<0, 0>(acc, xa, wa, xb, wb, patch, pk, wl, [&](int st) {
                             if (st == 0) { weights_one(0); weights_one(1); }
                             if (st == 1) { weights_one(2); weights_one(3); }
                             if (st == 2) { patch_one(0); patch_one(1); }
@@ -1135,15 +996,13 @@ conv3x3_bf16_mq_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, con
                             if (st == 4) { patch_one(4); patch_one(5); }
                         });
                     if (k == 1)
-                        mq_steps<1, 0, PRIO>(acc, xa, wa, xb, wb, patch, pk, wl, [&](int st) {
+                        mq_steps<1, 0>(acc, xa, wa, xb, wb, patch, pk, wl, [&](int st) {
                             if (st == 0) { weights_one(0); weights_one(1); }
                             if (st == 1) { weights_one(2); weights_one(3); }
                         });
                 }
             }
         }
-        if constexpr (PRIO != 0) __builtin_amdgcn_s_setprio(0);
-        stamp(2);
         if (pt == Cf::PARTS - 1 && q == nq - 1) {
             int t0, f0; int64_t b;
             tile_coords(ps / nq, t0, f0, b);
@@ -1165,18 +1024,9 @@ conv3x3_bf16_mq_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, con
                     store8(yp + co, y);
                 }
             }
-            stamp(5);
         }
     }
     wait_vmcnt<0>();                                         // the surplus LDS-DMA of the last stages lands before the wave ends
-    if constexpr (STAMP) {
-        if (lane == 0 && stamps) {
-            unsigned long long* o = stamps + ((size_t)blockIdx.x * 8 + wave) * 8;
-            for (int k = 0; k < 6; ++k) o[k] = tacc[k];
-            o[6] = clock_cycles() - tk0;
-            o[7] = clock_100mhz() - tr0;
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1238,24 +1088,11 @@ __device__ __forceinline__ void m0_steps(f32x4 (&acc)[3][3], bf16x8 (&xa)[3], bf
     }
 }
 
-template <bool STAMP = false, bool DEFER = false>
 __global__ void __launch_bounds__(kBigThreads, 2)
 conv3x3_bf16_m0_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf16_t* __restrict__ Wp, const float* __restrict__ scale,
                        const float* __restrict__ shift, const bf16_t* __restrict__ zero_page, int Th, int Fw, int Cin, int Cout, int tiles_t,
-                       int tiles_f, int ntiles, unsigned long long* __restrict__ stamps = nullptr) {
+                       int tiles_f, int ntiles) {
     typedef ConvM0 Cf;
-    unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0}, tk0 = 0, tr0 = 0, tlast = 0;
-    auto stamp = [&](int k) {
-        if constexpr (STAMP) {
-            const unsigned long long now = clock_cycles();
-            tacc[k] += now - tlast;
-            tlast = now;
-        }
-    };
-    if constexpr (STAMP) {
-        tk0 = tlast = clock_cycles();
-        tr0 = clock_100mhz();
-    }
     bf16_t* const patch0 = reinterpret_cast<bf16_t*>(alsep_smem);
     bf16_t* const wts = patch0 + (size_t)2 * Cf::PBUF * 8;
     float* ss = reinterpret_cast<float*>(alsep_smem + Cf::ring_bytes);
@@ -1336,11 +1173,6 @@ conv3x3_bf16_m0_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, con
 #pragma unroll
         for (int j = 0; j < Cf::PJ; ++j) patch_one(j);
     }
-    // DEFER (experiment, off): the epilogue of the younger half of the workgroup (waves 4-7) behind the next tile's barrier.  The older
-    // wave of a SIMD wins every arbitration: waves 0-3 leave the k-loop ~2,000 cycles before waves 4-7 and store their rows while those
-    // still compute; waves 4-7's stores sit on the critical path in front of the barrier (stamps: 15-18 % of the launch).  Deferred they
-    // were meant to overlap the older half's next k-loop -- measured: their 6 stores then take 2,900 instead of 1,000 cycles per tile
-    // (issued beside the older half's LDS-DMA burst) and the launch goes from 233 to 265 us.
     auto epilogue = [&](int k) {
         int t0, f0; int64_t b;
         tile_coords(k, t0, f0, b);
@@ -1371,17 +1203,11 @@ conv3x3_bf16_m0_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, con
             }
         }
     };
-    const bool late = DEFER && wave >= 4;
     for (int k = 0; k < my_tiles; ++k) {
-        // in flight, oldest first: [this tile's patch (and, k = 0, the weights)] [waves that store before the barrier: the ST stores of
-        // the previous tile].  A deferring wave's stores were issued before the patch pieces: nothing younger than the patch.
-        if (k > 0 && !late) wait_vmcnt<ST>();
+        // in flight, oldest first: [this tile's patch (and, k = 0, the weights)] [the ST stores of the previous tile]
+        if (k > 0) wait_vmcnt<ST>();
         else wait_vmcnt<0>();
-        stamp(0);
         barrier_nodrain();
-        stamp(1);
-        if (late && k > 0) epilogue(k - 1);
-        stamp(3);
         patch_prep(k + 1);
 #pragma unroll
         for (int b = 0; b < 3; ++b)
@@ -1394,20 +1220,9 @@ conv3x3_bf16_m0_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, con
                 if (st < Cf::PJ) patch_one(st);              // the next tile's patch, one piece per k-step
             });
         }
-        stamp(2);
-        if (!late) epilogue(k);
-        stamp(5);
+        epilogue(k);
     }
-    if (late && my_tiles > 0) epilogue(my_tiles - 1);
     wait_vmcnt<0>();
-    if constexpr (STAMP) {
-        if (lane == 0 && stamps) {
-            unsigned long long* o = stamps + ((size_t)blockIdx.x * 8 + wave) * 8;
-            for (int k = 0; k < 6; ++k) o[k] = tacc[k];
-            o[6] = clock_cycles() - tk0;
-            o[7] = clock_100mhz() - tr0;
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1848,11 +1663,6 @@ __device__ __forceinline__ void tdfw_read_x(bf16x8 (&xf)[3], const bf16_t* base)
     xf[2] = tdfw_read_frag<OFF + 64>(base);
 }
 
-// timing-only ablation of the wide kernel (variant libraries built with -DALSEP_TDF_ABL=n, never the product; results are wrong):
-// bit 0 the weight fragments of the first K tile are reused for all tiles, bit 1 no residual loads, bit 2 no X tiles beyond the first two
-#ifndef ALSEP_TDF_ABL
-#define ALSEP_TDF_ABL 0
-#endif
 // FINAL (last block of the network, C == 48 so that a unit is one frame with all its channels): the rounded output rows are
 // not stored; they stay in this wave's LDS, where each of the 48 pixels (one f' row) is reduced over its 48 channels exactly
 // as final_conv_kernel does it -- y[r] = bias[r], fmaf over ci ascending, one float32 chain per (pixel, r), then * alpha --
@@ -1938,7 +1748,7 @@ tdf_bf16_wide_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const
 #pragma unroll
         for (int ni = 0; ni < 3; ++ni)
 #pragma unroll
-            for (int mi = 0; mi < 3; ++mi) mma_step(acc[u][ni][mi], xf[ni], wf[(ALSEP_TDF_ABL & 1) ? 0 : par][ks][mi]);
+            for (int mi = 0; mi < 3; ++mi) mma_step(acc[u][ni][mi], xf[ni], wf[par][ks][mi]);
     };
     // tile it sits in stage S_ (= it % 3), its weights in wf[P_] (P_ = it % 2); all indices compile-time
 #define ALSEP_TDFW_STEP(it_, S_, P_)                                                              \
@@ -1946,8 +1756,8 @@ tdf_bf16_wide_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const
         wait_vmcnt<Tc::GLDS>();            /* all but X(it+1): W(it) and X(it) have landed */     \
         if ((it_) + 1 >= ntile) wait_vmcnt<0>();         /* last tile: nothing was issued behind */ \
         barrier_nodrain();                 /* every wave's part of X(it); compute(it-1) finished */ \
-        if ((it_) + 1 < ntile && !(ALSEP_TDF_ABL & 1)) issue_w((it_) + 1, 1 - (P_));              \
-        if ((it_) + 2 < ntile && !(ALSEP_TDF_ABL & 4)) issue_x((it_) + 2, ((S_) + 2) % 3);        \
+        if ((it_) + 1 < ntile) issue_w((it_) + 1, 1 - (P_));                                     \
+        if ((it_) + 2 < ntile) issue_x((it_) + 2, ((S_) + 2) % 3);                               \
         const bf16_t* xs_ = xlane + (size_t)(S_) * Tc::STAGE_ELEMS;                               \
         bf16x8 xa[3], xb[3];                                                                      \
         tdfw_read_x<0, 0>(xa, xs_);                                                               \
@@ -2025,7 +1835,7 @@ tdf_bf16_wide_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const
         for (int it = 0; it < 5; ++it)
             if (it * 64 + lane < Tc::TR * 6) rr[u][it] = *reinterpret_cast<const ALSEP_GLOBAL bf16x8*>(rb + loff[it]);
     };
-    if (RESIDUAL && !(ALSEP_TDF_ABL & 2)) {
+    if (RESIDUAL) {
 #pragma unroll
         for (int u = 0; u < PF && u < Tc::UN; ++u) {
             load_res(u);
@@ -2038,7 +1848,7 @@ tdf_bf16_wide_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const
 #pragma unroll
     for (int u = 0; u < Tc::UN; ++u) {
         const int cb = (int)((u0 + u) % upc) * Tc::UC;
-        if (RESIDUAL && u + PF < Tc::UN && !(ALSEP_TDF_ABL & 2)) load_res(u + PF);
+        if (RESIDUAL && u + PF < Tc::UN) load_res(u + PF);
         ALSEP_GLOBAL char* yb = const_cast<ALSEP_GLOBAL char*>(opaque_uniform_gptr(reinterpret_cast<const char*>(Y + unit_base(u))));
 #pragma unroll
         for (int ni = 0; ni < 3; ++ni) {
@@ -3004,8 +2814,7 @@ struct DevBuf {
 
 struct ConvLayer {       // 3x3
     DevBuf w, scale, shift;
-    DevBuf w_big;            // conv3x3_bf16_big_kernel's image (c = 96 / 144): rows in ConvBig::channel_of_row order
-    DevBuf w_mny;            // conv3x3_bf16_mny_kernel's image (c = 96 / 144)
+    DevBuf w_big;            // rows in ConvBig::channel_of_row order: conv3x3_bf16_m0_kernel's image (c = 48), conv3x3_bf16_big_kernel<3>'s (c = 144)
     DevBuf w_mq;             // conv3x3_bf16_mq_kernel's image (c = 96)
     int cin = 0, cout = 0;
     bool dma_path = false;   // packed for conv3x3_bf16_kernel (swizzled, unpadded)
@@ -3133,34 +2942,6 @@ std::vector<bf16_t> pack_conv3x3_big(const std::vector<float>& w, int cin) {
     return pack_conv3x3_dma(wp, cin, cout);
 }
 
-#ifdef ALSEP_EXPERIMENTS
-// image of conv3x3_bf16_mny_kernel<NY>: [q][kt][48 NY rows][WG groups][8]; row R holds output channel ConvBig::channel_of_row(R);
-// group (k-step stl of part kt, lq) sits at 4 stl + (lq ^ wswz(R)) and holds k-group 4 (kt KS + stl) + lq of the chunk (tap-major,
-// 6 groups of 8 input channels per tap; groups >= 54 are zero)
-template <int NY>
-std::vector<bf16_t> pack_conv3x3_mny(const std::vector<float>& w, int cin) {
-    typedef ConvMny<NY> Cf;
-    const int nq = cin / Cf::KC;
-    std::vector<bf16_t> out((size_t)nq * Cf::PARTS * Cf::WGROUPS * 8, host_cast<bf16_t>(0.f));
-    for (int q = 0; q < nq; ++q)
-        for (int kt = 0; kt < Cf::PARTS; ++kt)
-            for (int R = 0; R < Cf::ROWS; ++R)
-                for (int stl = 0; stl < Cf::ksteps_of_part(kt); ++stl)
-                    for (int lq = 0; lq < 4; ++lq) {
-                        const int grp = 4 * (kt * Cf::KS + stl) + lq;
-                        if (grp >= Cf::NG) continue;
-                        const int tap = grp / Cf::CG, cg = grp % Cf::CG, co = ConvBig<NY>::channel_of_row(R);
-                        const size_t dst = ((((size_t)q * Cf::PARTS + kt) * Cf::ROWS + R) * Cf::WG + 4 * stl + (lq ^ Cf::wswz(R))) * 8;
-                        for (int e = 0; e < 8; ++e) {
-                            const int ci = q * Cf::KC + cg * 8 + e;
-                            out[dst + e] = host_cast<bf16_t>(w[(((size_t)co * cin + ci) * 3 + tap / 3) * 3 + tap % 3]);
-                        }
-                    }
-    return out;
-}
-
-#endif  // ALSEP_EXPERIMENTS
-
 // image of conv3x3_bf16_mq_kernel (c_out = 96): [q][part][96 rows][20 groups][8]; k-step stl of part pt is tap 5 pt + stl, its group lq
 // (input channels 32 q + 8 lq ..) sits at 4 stl + (lq ^ wswz(R)); row R holds output channel ConvBig<2>::channel_of_row(R)
 std::vector<bf16_t> pack_conv3x3_mq(const std::vector<float>& w, int cin) {
@@ -3205,23 +2986,18 @@ int make_conv(alsep_net* net, const TensorMap& tm, const std::string& p, int c, 
         L->dma_path = true;
         auto pk = pack_conv3x3_dma(*w, c, c);
         rc = upload(net, pk.data(), pk.size() * sizeof(bf16_t), &L->w);
-        if (!rc && (c == 96 || c == 144)) {                  // a second image for the big-tile kernel (its own output-channel order)
-            auto pb = c == 96 ? pack_conv3x3_big<2>(*w, c) : pack_conv3x3_big<3>(*w, c);
-            rc = upload(net, pb.data(), pb.size() * sizeof(bf16_t), &L->w_big);
-#ifdef ALSEP_EXPERIMENTS
-            if (!rc) {
-                auto pm = c == 96 ? pack_conv3x3_mny<2>(*w, c) : pack_conv3x3_mny<3>(*w, c);
-                rc = upload(net, pm.data(), pm.size() * sizeof(bf16_t), &L->w_mny);
-            }
-#endif
-            if (!rc && c == 96) {
-                auto pq = pack_conv3x3_mq(*w, c);
-                rc = upload(net, pq.data(), pq.size() * sizeof(bf16_t), &L->w_mq);
-            }
-        }
-        if (!rc && c == 48) {                                // level 0: the LDS-resident-weight kernel's image (its own output-channel order)
+        // a second image for the level's 8-wave persistent kernel (its own output-channel order)
+        if (!rc && c == 48) {                                // level 0: the LDS-resident-weight kernel
             auto p0 = pack_conv3x3_big<1>(*w, c);
             rc = upload(net, p0.data(), p0.size() * sizeof(bf16_t), &L->w_big);
+        }
+        if (!rc && c == 96) {                                // level 1: the double-buffered kernel
+            auto pq = pack_conv3x3_mq(*w, c);
+            rc = upload(net, pq.data(), pq.size() * sizeof(bf16_t), &L->w_mq);
+        }
+        if (!rc && c == 144) {                               // level 2: the big-tile kernel
+            auto pb = pack_conv3x3_big<3>(*w, c);
+            rc = upload(net, pb.data(), pb.size() * sizeof(bf16_t), &L->w_big);
         }
     } else if (conv_uses_main<T>(c, c)) {
         auto pk = pack_conv3x3<T, ConvSel<T>::KC, ConvSel<T>::BN>(*w, c, c);
@@ -3441,27 +3217,8 @@ int run_conv_tw(alsep_ctx* ctx, const ConvLayer& L, const T* X, T* Y, int64_t B,
     return launch_conv<T, KC, BN, 16>(ctx, L, X, Y, B, Th, Fw);
 }
 
-// timing-only diagnostic (ALSEP_CONV_ABLATE=1|2|4: skip LDS-DMA / MFMA loop / stores); results are wrong when set
-// The product build has no switch that changes WHAT is computed: the work-skipping (ablation), staggering, stamped and superseded
-// kernel variants below exist only in a library compiled with -DALSEP_EXPERIMENTS (ALSEP_BUILD_EXPERIMENTS=1 python -c
-// 'import __graft_entry__ as g; g.build(force=True)'; alsep_experiments_enabled() tells which one is loaded).
-#ifdef ALSEP_EXPERIMENTS
-int conv_ablate() {
-    static const int v = [] { const char* e = getenv("ALSEP_CONV_ABLATE"); return e ? atoi(e) : 0; }();
-    return v;
-}
-
-int conv_stagger() {
-    static const int v = [] { const char* e = getenv("ALSEP_CONV_STAGGER"); return e ? atoi(e) : 0; }();
-    return v;
-}
-#else
-constexpr int conv_ablate() { return 0; }
-constexpr int conv_stagger() { return 0; }
-#endif
-
 int conv_ny_fastest() {
-    static const int v = [] { const char* e = getenv("ALSEP_CONV_NYFAST"); return e ? atoi(e) : 1; }();
+    static const int v = env_int("ALSEP_CONV_NYFAST", 1);
     return v;
 }
 
@@ -3481,7 +3238,7 @@ int launch_conv_dma(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t*
     hipLaunchKernelGGL((conv3x3_bf16_kernel<TW>), ny_fastest ? dim3((unsigned)(ntiles * nyc)) : dim3((unsigned)ntiles, nyc),
                        dim3(kThreads), Cf::lds_bytes,
                        ctx->stream, X, Y, (const bf16_t*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page,
-                       Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles, conv_ablate(), conv_stagger(), ny_fastest);
+                       Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles, /*ablate*/ 0, /*stagger*/ 0, ny_fastest);
     note_launch(ctx, TW == 64 ? "conv3x3_bf16_kernel<64>" : "conv3x3_bf16_kernel<small>");
     ALSEP_LAUNCH_CHECK(ctx, "conv3x3_bf16_kernel");
     return ALSEP_OK;
@@ -3508,378 +3265,98 @@ int launch_conv_regw(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t
     return ALSEP_OK;
 }
 
-#ifdef ALSEP_EXPERIMENTS
-template <int NY>
-int launch_conv_pipe(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B,
-                     int Th, int Fw) {
-    typedef ConvPipe<NY> Cf;
+// The three 8-wave persistent convs (conv3x3_bf16_m0_kernel, _mq_kernel, _big_kernel<3>) share their argument list and their launch: one
+// workgroup per CU, each walking the tiles blockIdx.x, blockIdx.x + gridDim.x, ...  Cf is the kernel's tile configuration, wimg its weight
+// image; the caller has checked that the layer fits the kernel.
+template <typename Cf, typename Kern>
+int launch_conv_persist(alsep_ctx* ctx, Kern kern, const ConvLayer& L, const DevBuf& wimg, int prof_class, const char* name, const bf16_t* X,
+                        bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
     const int tiles_t = Th / Cf::TH, tiles_f = Fw / Cf::TW;
     const int64_t ntiles = B * tiles_t * tiles_f;
     if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
-    ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_pipe_kernel<NY>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)Cf::lds_bytes));
-    const int gx = ntiles < 256 ? (int)ntiles : 256;        // one persistent workgroup per CU
-    ProfScope prof(ctx, ALSEP_PROF_CONV3X3_PIPE);
+    ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
+    const int gx = ntiles < 256 ? (int)ntiles : 256;
+    ProfScope prof(ctx, prof_class);
     prof.work(18.0 * (double)L.cin * L.cout * B * Th * Fw, (double)sizeof(*X) * B * Th * Fw * (L.cin + L.cout));
-    hipLaunchKernelGGL((conv3x3_bf16_pipe_kernel<NY>), dim3((unsigned)gx), dim3(kThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                       (const bf16_t*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin,
-                       L.cout, tiles_t, tiles_f, (int)ntiles);
-    ALSEP_LAUNCH_CHECK(ctx, "conv3x3_bf16_pipe_kernel");
+    hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y, (const bf16_t*)wimg.p,
+                       (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles);
+    ALSEP_LAUNCH_CHECK(ctx, name);
     return ALSEP_OK;
 }
-#endif  // ALSEP_EXPERIMENTS
 
-#if defined(ALSEP_EXPERIMENTS) && !defined(ALSEP_CPU_EMUL)
-// timing experiments: print the per-phase cycle sums a stamped conv kernel left in dbuf [workgroup][wave][8]
-int report_stamps(alsep_ctx* ctx, unsigned long long* dbuf, int gx, int stages, long long ntiles, const char* label) {
-    const size_t n = (size_t)256 * 8 * 8;
-    ALSEP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<unsigned long long> h(n);
-    ALSEP_HIP(ctx, hipMemcpy(h.data(), dbuf, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    double mean[8] = {0};
-    for (int w = 0; w < gx * 8; ++w)
-        for (int k = 0; k < 8; ++k) mean[k] += (double)h[(size_t)w * 8 + k] / (gx * 8);
-    fprintf(stderr, "[%s stamp] tiles %lld grid %d stages/wg %d | cycles/wave: vmwait %.0f barrier %.0f kloop %.0f pbarrier %.0f pissue %.0f "
-                    "epilogue %.0f total %.0f | %.2f GHz | per stage: vmwait %.0f barrier %.0f kloop %.0f (MFMA floor %d)\n", label, ntiles,
-            gx, stages, mean[0], mean[1], mean[2], mean[3], mean[4], mean[5], mean[6], mean[6] / (mean[7] * 10.0), mean[0] / stages,
-            mean[1] / stages, mean[2] / stages, 2 * 14 * 12 * 16);
-    for (int w : {0, 4, 7})
-        fprintf(stderr, "    wg0 wave %d: vmwait %llu barrier %llu kloop %llu pbarrier %llu pissue %llu epilogue %llu total %llu\n", w,
-                h[w * 8 + 0], h[w * 8 + 1], h[w * 8 + 2], h[w * 8 + 3], h[w * 8 + 4], h[w * 8 + 5], h[w * 8 + 6]);
-    return ALSEP_OK;
-}
-unsigned long long* stamp_buffer(alsep_ctx* ctx) {
-    static unsigned long long* dbuf = nullptr;
-    if (!dbuf && hipMalloc(&dbuf, (size_t)256 * 8 * 8 * sizeof(unsigned long long)) != hipSuccess) dbuf = nullptr;
-    if (dbuf) (void)hipMemsetAsync(dbuf, 0, (size_t)256 * 8 * 8 * sizeof(unsigned long long), ctx->stream);
-    return dbuf;
-}
-#endif
-
-template <int NY>
-int launch_conv_big(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B,
-                    int Th, int Fw) {
-    typedef ConvBig<NY> Cf;
-    const int tiles_t = Th / Cf::TH, tiles_f = Fw / Cf::TW;
-    const int64_t ntiles = B * tiles_t * tiles_f;
-    if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
+int launch_conv_big3(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
     if (!L.w_big.p) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no big-tile weight image for this layer");
-    ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_big_kernel<NY, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)Cf::lds_bytes));
-    const int gx = ntiles < 256 ? (int)ntiles : 256;
-    // ALSEP_CONV_BIG_SWP: 0 (default) rolled k-loop; 1 software-pipelined k-loop at NY = 2; 2 also at NY = 3 (spills).  Same-box A/B
-    // (profiles/r02_conv_big_swp_ab.txt): the pipelined loop takes 3-7 % off this kernel (310 -> 301 / 287 us) but the whole step gets
-    // SLOWER (233.5 -> 238.4 ms): every other kernel -- the untouched NY = 3 conv, the plain conv, even the stand-alone STFT loop that
-    // runs after the steps -- loses 5-9 % in the same process.  The chip gives the saved stall cycles back as a lower clock
-    // (MI355X_MICROARCH.md, DVFS give-back), and keeps it lower for the kernels that follow.
-#ifdef ALSEP_EXPERIMENTS
-    static const int swp = [] { const char* e = getenv("ALSEP_CONV_BIG_SWP"); return e ? atoi(e) : 0; }();
-#else
-    constexpr int swp = 0;
-#endif
-    ProfScope prof(ctx, NY == 3 ? ALSEP_PROF_CONV3X3_BIG3 : ALSEP_PROF_CONV3X3_BIG);
-    prof.work(18.0 * (double)L.cin * L.cout * B * Th * Fw, (double)sizeof(*X) * B * Th * Fw * (L.cin + L.cout));
-#if defined(ALSEP_EXPERIMENTS) && !defined(ALSEP_CPU_EMUL)
-    // ALSEP_CONV_BIG_STAMP=n (timing experiments): the first n launches run the stamped variant, synchronise and print the per-phase
-    // cycle sums (mean over waves, and waves 0 / 7 of workgroup 0) to stderr
-    static int stamp_left = [] { const char* e = getenv("ALSEP_CONV_BIG_STAMP"); return e ? atoi(e) : 0; }();
-    if (stamp_left > 0) {
-        --stamp_left;
-        unsigned long long* dbuf = stamp_buffer(ctx);
-        if (!dbuf) return alsep_fail(ctx, ALSEP_ERR_NOMEM, "stamp buffer");
-        static const int abl = [] { const char* e = getenv("ALSEP_CONV_BIG_ABL"); return e ? atoi(e) : 0; }();
-        auto go = [&](auto kern) -> int {
-            ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-            hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y, (const bf16_t*)L.w_big.p,
-                               (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles,
-                               dbuf);
-            return ALSEP_OK;
-        };
-        int grc = ALSEP_OK;
-        if (NY != 2 || abl == 0) grc = go(conv3x3_bf16_big_kernel<NY, false, true, 0>);
-        else if constexpr (NY == 2) {
-            switch (abl) {
-                case 1: grc = go(conv3x3_bf16_big_kernel<2, false, true, 1>); break;
-                case 2: grc = go(conv3x3_bf16_big_kernel<2, false, true, 2>); break;
-                case 4: grc = go(conv3x3_bf16_big_kernel<2, false, true, 4>); break;
-                case 6: grc = go(conv3x3_bf16_big_kernel<2, false, true, 6>); break;
-                case 7: grc = go(conv3x3_bf16_big_kernel<2, false, true, 7>); break;
-                case 8: grc = go(conv3x3_bf16_big_kernel<2, false, true, 8>); break;
-                case 16: grc = go(conv3x3_bf16_big_kernel<2, false, true, 16>); break;
-                case 32: grc = go(conv3x3_bf16_big_kernel<2, false, true, 32>); break;
-                case 100: grc = go(conv3x3_bf16_big_kernel<2, true, true, 0>); break;      // the software-pipelined loop, stamped
-                default: return alsep_fail(ctx, ALSEP_ERR_ARG, "ALSEP_CONV_BIG_ABL: 1, 2, 4, 6, 7, 8, 16, 32 or 100");
-            }
-        }
-        if (grc) return grc;
-        ALSEP_LAUNCH_CHECK(ctx, "conv3x3_bf16_big_kernel");
-        const int stages = (int)((ntiles + gx - 1) / gx) * NY * (L.cin / Cf::KC);
-        char label[64];
-        snprintf(label, sizeof label, "big<%d> abl %d", NY, abl);
-        if (int rrc = report_stamps(ctx, dbuf, gx, stages, (long long)ntiles, label)) return rrc;
-        note_launch(ctx, NY == 3 ? "conv3x3_bf16_big_kernel<3>" : "conv3x3_bf16_big_kernel<2>");
-        return ALSEP_OK;
-    }
-#endif
-#ifdef ALSEP_EXPERIMENTS
-    if (swp >= (NY == 2 ? 1 : 2)) {                          // NY = 3: the second fragment set does not fit 256 registers (76 spilled): opt-in only
-        ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_big_kernel<NY, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)Cf::lds_bytes));
-        hipLaunchKernelGGL((conv3x3_bf16_big_kernel<NY, true>), dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                           (const bf16_t*)L.w_big.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin,
-                           L.cout, tiles_t, tiles_f, (int)ntiles);
-    } else
-#endif
-    {
-        hipLaunchKernelGGL((conv3x3_bf16_big_kernel<NY, false>), dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                           (const bf16_t*)L.w_big.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin,
-                           L.cout, tiles_t, tiles_f, (int)ntiles);
-    }
-    note_launch(ctx, NY == 3 ? "conv3x3_bf16_big_kernel<3>" : "conv3x3_bf16_big_kernel<2>");
-    ALSEP_LAUNCH_CHECK(ctx, "conv3x3_bf16_big_kernel");
+    if (int rc = launch_conv_persist<ConvBig<3>>(ctx, conv3x3_bf16_big_kernel<3>, L, L.w_big, ALSEP_PROF_CONV3X3_BIG3, "conv3x3_bf16_big_kernel",
+                                                 X, Y, zero_page, B, Th, Fw))
+        return rc;
+    note_launch(ctx, "conv3x3_bf16_big_kernel<3>");
     return ALSEP_OK;
 }
-
-#ifdef ALSEP_EXPERIMENTS
-template <int NY>
-int launch_conv_mny(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
-    typedef ConvMny<NY> Cf;
-    const int tiles_t = Th / Cf::TH, tiles_f = Fw / Cf::TW;
-    const int64_t ntiles = B * tiles_t * tiles_f;
-    if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
-    if (!L.w_mny.p) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no merged-kernel weight image for this layer");
-    ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_mny_kernel<NY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-    const int gx = ntiles < 256 ? (int)ntiles : 256;
-    ProfScope prof(ctx, NY == 3 ? ALSEP_PROF_CONV3X3_BIG3 : ALSEP_PROF_CONV3X3_BIG);
-    prof.work(18.0 * (double)L.cin * L.cout * B * Th * Fw, (double)sizeof(*X) * B * Th * Fw * (L.cin + L.cout));
-#if defined(ALSEP_EXPERIMENTS) && !defined(ALSEP_CPU_EMUL)
-    static int stamp_left = [] { const char* e = getenv("ALSEP_CONV_BIG_STAMP"); return e ? atoi(e) : 0; }();
-    if (stamp_left > 0) {
-        --stamp_left;
-        unsigned long long* dbuf = stamp_buffer(ctx);
-        if (!dbuf) return alsep_fail(ctx, ALSEP_ERR_NOMEM, "stamp buffer");
-        static const int abl = [] { const char* e = getenv("ALSEP_CONV_BIG_ABL"); return e ? atoi(e) : 0; }();
-        auto go = [&](auto kern) -> int {
-            ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-            hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y, (const bf16_t*)L.w_mny.p,
-                               (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles,
-                               dbuf);
-            return ALSEP_OK;
-        };
-        int grc = ALSEP_OK;
-        switch (abl) {
-            case 1: grc = go(conv3x3_bf16_mny_kernel<NY, true, 1>); break;
-            case 2: grc = go(conv3x3_bf16_mny_kernel<NY, true, 2>); break;
-            case 3: grc = go(conv3x3_bf16_mny_kernel<NY, true, 3>); break;
-            case 4: grc = go(conv3x3_bf16_mny_kernel<NY, true, 4>); break;
-            case 7: grc = go(conv3x3_bf16_mny_kernel<NY, true, 7>); break;
-            default: grc = go(conv3x3_bf16_mny_kernel<NY, true, 0>); break;
-        }
-        if (grc) return grc;
-        ALSEP_LAUNCH_CHECK(ctx, NY == 3 ? "conv3x3_bf16_mny_kernel<3>" : "conv3x3_bf16_mny_kernel<2>");
-        char label[64];
-        snprintf(label, sizeof label, "mny<%d> abl %d", NY, abl);
-        return report_stamps(ctx, dbuf, gx, (int)((ntiles + gx - 1) / gx) * Cf::PARTS * (L.cin / Cf::KC), (long long)ntiles, label);
-    }
-#endif
-    hipLaunchKernelGGL((conv3x3_bf16_mny_kernel<NY>), dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                       (const bf16_t*)L.w_mny.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t,
-                       tiles_f, (int)ntiles);
-    ALSEP_LAUNCH_CHECK(ctx, NY == 3 ? "conv3x3_bf16_mny_kernel<3>" : "conv3x3_bf16_mny_kernel<2>");
-    return ALSEP_OK;
-}
-#endif  // ALSEP_EXPERIMENTS
 
 int launch_conv_mq(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
-    typedef ConvMq Cf;
-    const int tiles_t = Th / Cf::TH, tiles_f = Fw / Cf::TW;
-    const int64_t ntiles = B * tiles_t * tiles_f;
-    if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
-    if (!L.w_mq.p || L.cout != Cf::ROWS || L.cin % Cf::KC) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no mq weight image for this layer");
-    const int gx = ntiles < 256 ? (int)ntiles : 256;
-    ProfScope prof(ctx, ALSEP_PROF_CONV3X3_BIG);
-    prof.work(18.0 * (double)L.cin * L.cout * B * Th * Fw, (double)sizeof(*X) * B * Th * Fw * (L.cin + L.cout));
-#if defined(ALSEP_EXPERIMENTS) && !defined(ALSEP_CPU_EMUL)
-    static int stamp_left = [] { const char* e = getenv("ALSEP_CONV_BIG_STAMP"); return e ? atoi(e) : 0; }();
-    if (stamp_left > 0) {
-        --stamp_left;
-        unsigned long long* dbuf = stamp_buffer(ctx);
-        if (!dbuf) return alsep_fail(ctx, ALSEP_ERR_NOMEM, "stamp buffer");
-        static const int sprio = [] { const char* e = getenv("ALSEP_CONV_MQ_PRIO"); return e ? atoi(e) : 0; }();
-        if (sprio) {
-            ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_mq_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-            hipLaunchKernelGGL((conv3x3_bf16_mq_kernel<true, 1>), dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                               (const bf16_t*)L.w_mq.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t,
-                               tiles_f, (int)ntiles, dbuf);
-        } else {
-            ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_mq_kernel<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-            hipLaunchKernelGGL((conv3x3_bf16_mq_kernel<true, 0>), dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                               (const bf16_t*)L.w_mq.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t,
-                               tiles_f, (int)ntiles, dbuf);
-        }
-        ALSEP_LAUNCH_CHECK(ctx, "conv3x3_bf16_mq_kernel");
-        return report_stamps(ctx, dbuf, gx, (int)((ntiles + gx - 1) / gx) * Cf::PARTS * (L.cin / Cf::KC), (long long)ntiles, sprio ? "mq prio" : "mq");
-    }
-#endif
-#ifdef ALSEP_EXPERIMENTS
-    static const int prio = [] { const char* e = getenv("ALSEP_CONV_MQ_PRIO"); return e ? atoi(e) : 0; }();
-    if (prio) {
-        ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_mq_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-        hipLaunchKernelGGL((conv3x3_bf16_mq_kernel<false, 1>), dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                           (const bf16_t*)L.w_mq.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t,
-                           tiles_f, (int)ntiles, nullptr);
-        ALSEP_LAUNCH_CHECK(ctx, "conv3x3_bf16_mq_kernel");
-        return ALSEP_OK;
-    }
-#endif
-    ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_mq_kernel<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-    hipLaunchKernelGGL((conv3x3_bf16_mq_kernel<false, 0>), dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                       (const bf16_t*)L.w_mq.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t,
-                       tiles_f, (int)ntiles, nullptr);
-    ALSEP_LAUNCH_CHECK(ctx, "conv3x3_bf16_mq_kernel");
-    return ALSEP_OK;
+    if (!L.w_mq.p || L.cout != ConvMq::ROWS || L.cin % ConvMq::KC) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no mq weight image for this layer");
+    return launch_conv_persist<ConvMq>(ctx, conv3x3_bf16_mq_kernel, L, L.w_mq, ALSEP_PROF_CONV3X3_BIG, "conv3x3_bf16_mq_kernel", X, Y, zero_page,
+                                       B, Th, Fw);
 }
 
-// ALSEP_CONV_MQ (default 1): level-1 convs (c = 96) on the fully double-buffered kernel.  Same-box A/B at the bench shape
-// (profiles/r02_conv_level1_ab.txt): big-tile 316 us -> merged 262 us -> this 210-219 us per launch (1.13 PFLOP/s = 45 % of 2.5 PF)
 int launch_conv_m0(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
-    typedef ConvM0 Cf;
-    const int tiles_t = Th / Cf::TH, tiles_f = Fw / Cf::TW;
-    const int64_t ntiles = B * tiles_t * tiles_f;
-    if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
-    if (!L.w_big.p || L.cout != Cf::ROWS || L.cin != Cf::KC) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no m0 weight image for this layer");
-    const int gx = ntiles < 256 ? (int)ntiles : 256;
-#ifdef ALSEP_EXPERIMENTS
-    static const int defer = [] { const char* e = getenv("ALSEP_CONV_M0_DEFER"); return e ? atoi(e) : 0; }();
-#else
-    constexpr int defer = 0;
-#endif
-    ProfScope prof(ctx, ALSEP_PROF_CONV3X3_REGW);
-    prof.work(18.0 * (double)L.cin * L.cout * B * Th * Fw, (double)sizeof(*X) * B * Th * Fw * (L.cin + L.cout));
-#if defined(ALSEP_EXPERIMENTS) && !defined(ALSEP_CPU_EMUL)
-    static int stamp_left = [] { const char* e = getenv("ALSEP_CONV_M0_STAMP"); return e ? atoi(e) : 0; }();
-    if (stamp_left > 0) {
-        --stamp_left;
-        unsigned long long* dbuf = stamp_buffer(ctx);
-        if (!dbuf) return alsep_fail(ctx, ALSEP_ERR_NOMEM, "stamp buffer");
-        if (defer) {
-            ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_m0_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-            hipLaunchKernelGGL((conv3x3_bf16_m0_kernel<true, true>), dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                               (const bf16_t*)L.w_big.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t,
-                               tiles_f, (int)ntiles, dbuf);
-        } else {
-            ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_m0_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-            hipLaunchKernelGGL((conv3x3_bf16_m0_kernel<true, false>), dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                               (const bf16_t*)L.w_big.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t,
-                               tiles_f, (int)ntiles, dbuf);
-        }
-        ALSEP_LAUNCH_CHECK(ctx, "conv3x3_bf16_m0_kernel");
-        return report_stamps(ctx, dbuf, gx, (int)((ntiles + gx - 1) / gx), (long long)ntiles, defer ? "m0 defer" : "m0");
-    }
-#endif
-#ifdef ALSEP_EXPERIMENTS
-    if (defer) {
-        ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_m0_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-        hipLaunchKernelGGL((conv3x3_bf16_m0_kernel<false, true>), dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                           (const bf16_t*)L.w_big.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t,
-                           tiles_f, (int)ntiles, nullptr);
-    } else
-#endif
-    {
-        (void)defer;
-        ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_m0_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-        hipLaunchKernelGGL((conv3x3_bf16_m0_kernel<false, false>), dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                           (const bf16_t*)L.w_big.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t,
-                           tiles_f, (int)ntiles, nullptr);
-    }
-    ALSEP_LAUNCH_CHECK(ctx, "conv3x3_bf16_m0_kernel");
-    return ALSEP_OK;
+    if (!L.w_big.p || L.cout != ConvM0::ROWS || L.cin != ConvM0::KC) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no m0 weight image for this layer");
+    return launch_conv_persist<ConvM0>(ctx, conv3x3_bf16_m0_kernel, L, L.w_big, ALSEP_PROF_CONV3X3_REGW, "conv3x3_bf16_m0_kernel", X, Y, zero_page,
+                                       B, Th, Fw);
 }
 
-// ALSEP_CONV_M0 (default 1): level-0 convs (c = 48, T % 8 == 0, F % 48 == 0, >= 256 tiles) on the LDS-resident-weight kernel; same-box
-// A/B at the bench shape (profiles/r02_conv_level0_ab.txt): register-weight kernel 268.5 us -> 233 us per 1.12 GB launch (4.8 TB/s = 60 % of 8
-// TB/s).  ALSEP_CONV_M0_DEFER=1 (waves 4-7 store behind the next barrier) measured slower (265 us): off.
+// Which kernel runs a bf16 / f16 3x3 conv with c % 48 == 0.  Every switch is an environment variable read once per process; each one only
+// chooses between kernels that compute the same layer (all but mq bit-identically to the plain kernel).
+//   ALSEP_CONV_M0     1 (default): c = 48 with T % 8 == 0, F % 48 == 0 and >= 256 tiles on conv3x3_bf16_m0_kernel (LDS-resident weights);
+//                     2: without the minimum tile count (tests); 0: off.  Same-box A/B at the bench shape (profiles/r02_conv_level0_ab.txt):
+//                     register-weight kernel 268.5 us -> 233 us per 1.12 GB launch (4.8 TB/s = 60 % of 8 TB/s).
+//   ALSEP_CONV_REGW   what m0 leaves, with T % 4 == 0 and F % 64 == 0, on conv3x3_bf16_regw_kernel.  1 (default): c = 48 on 4 x 32 tiles, two
+//                     workgroups per CU; 2: also c = 96; 3: as 2, with c = 48 on 4 x 64 tiles, one workgroup per CU; 0: off.
+//   ALSEP_CONV_BIG    1 (default): c = 96 / 144 with T % 8 == 0, F % 64 == 0 and >= 96 tiles on the 8-wave kernel of its level (_MQ, _BIG3);
+//                     2: without the minimum tile count (tests); 0: off.
+//   ALSEP_CONV_MQ     1 (default): c = 96 on conv3x3_bf16_mq_kernel (everything double-buffered); 0: the plain kernel.  Same-box A/B at the
+//                     bench shape (profiles/r02_conv_level1_ab.txt): big-tile 316 us -> merged 262 us -> this 210-219 us per launch
+//                     (1.13 PFLOP/s = 45 % of 2.5 PF).
+//   ALSEP_CONV_BIG3   1 (default): c = 144 on conv3x3_bf16_big_kernel<3> (8 VGPRs spill, outside the MFMA loops); 0: the plain kernel.
+//   ALSEP_CONV_NYFAST 1 (default): the plain kernel's Cout / 48 workgroups of one tile run back to back on one XCD (1-D grid, needs
+//                     ntiles % 8 == 0); 0: the tile index is the fastest grid dimension.
+// Everything else -- c = 192 and up (NY = 4 spills heavily at 2 waves / SIMD with ROCm 7.2), shapes that miss a divisibility above -- runs
+// conv3x3_bf16_kernel<64 | 32 | 16>.
 int conv_m0_enabled() {
-    static const int v = [] { const char* e = getenv("ALSEP_CONV_M0"); return e ? atoi(e) : 1; }();
+    static const int v = env_int("ALSEP_CONV_M0", 1);
     return v;
 }
-
-int conv_mq_enabled() {
-    static const int v = [] { const char* e = getenv("ALSEP_CONV_MQ"); return e ? atoi(e) : 1; }();
-    return v;
-}
-
-// ALSEP_CONV_MNY: bit 0 the merged kernel at c = 96, bit 1 at c = 144 (default: see run_conv_dma)
-#ifdef ALSEP_EXPERIMENTS
-int conv_mny_enabled() {
-    static const int v = [] { const char* e = getenv("ALSEP_CONV_MNY"); return e ? atoi(e) : 0; }();
-    return v;
-}
-#endif
-
-int conv_big_enabled() {
-    static const int v = [] { const char* e = getenv("ALSEP_CONV_BIG"); return e ? atoi(e) : 1; }();
-    return v;
-}
-
-int conv_big3_enabled() {
-    static const int v = [] { const char* e = getenv("ALSEP_CONV_BIG3"); return e ? atoi(e) : 1; }();
-    return v;
-}
-
-#ifdef ALSEP_EXPERIMENTS
-int conv_pipe_enabled() {
-    // opt-in: bit-identical to the plain kernel but not faster on MI355X (profiles/r01_conv_variants.txt):
-    // the per-CU LDS-DMA intake, not the missing overlap, bounds these levels
-    static const int v = [] { const char* e = getenv("ALSEP_CONV_PIPE"); return e ? atoi(e) : 0; }();
-    return v;
-}
-#endif
-
 int conv_regw_enabled() {
-    static const int v = [] { const char* e = getenv("ALSEP_CONV_REGW"); return e ? atoi(e) : 1; }();
+    static const int v = env_int("ALSEP_CONV_REGW", 1);
+    return v;
+}
+int conv_big_enabled() {
+    static const int v = env_int("ALSEP_CONV_BIG", 1);
+    return v;
+}
+int conv_mq_enabled() {
+    static const int v = env_int("ALSEP_CONV_MQ", 1);
+    return v;
+}
+int conv_big3_enabled() {
+    static const int v = env_int("ALSEP_CONV_BIG3", 1);
     return v;
 }
 
 int run_conv_dma(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zp, int64_t B, int Th, int Fw) {
     if (conv_m0_enabled() && L.cin == 48 && L.cout == 48 && Th % 8 == 0 && Fw % 48 == 0 &&
-        (conv_m0_enabled() >= 2 || B * (Th / 8) * (Fw / 48) >= 256))          // =2: no minimum tile count (tests)
+        (conv_m0_enabled() >= 2 || B * (Th / 8) * (Fw / 48) >= 256))
         return launch_conv_m0(ctx, L, X, Y, zp, B, Th, Fw);
     if (conv_regw_enabled() && Th % 4 == 0 && Fw % 64 == 0 && L.cin == L.cout) {
-        if (L.cin == 48 && conv_regw_enabled() == 3) return launch_conv_regw<1>(ctx, L, X, Y, zp, B, Th, Fw);   // one workgroup per CU
-        if (L.cin == 48) return launch_conv_regw<1, 3, 2, 32>(ctx, L, X, Y, zp, B, Th, Fw);   // 4 x 32 tiles, two workgroups per CU
+        if (L.cin == 48 && conv_regw_enabled() == 3) return launch_conv_regw<1>(ctx, L, X, Y, zp, B, Th, Fw);
+        if (L.cin == 48) return launch_conv_regw<1, 3, 2, 32>(ctx, L, X, Y, zp, B, Th, Fw);
         if (L.cin == 96 && conv_regw_enabled() >= 2) return launch_conv_regw<2>(ctx, L, X, Y, zp, B, Th, Fw);
     }
     if (conv_big_enabled() && Th % 8 == 0 && Fw % 64 == 0 && L.cin == L.cout &&
-        (conv_big_enabled() >= 2 || B * (Th / 8) * (Fw / 64) >= 96)) {       // =2: no minimum tile count (tests)
-        switch (L.cout / 48) {
-            case 2:                                          // ALSEP_CONV_MQ=0: the plain kernel (experiments builds: merged / big-tile NY = 2)
-                if (conv_mq_enabled()) return launch_conv_mq(ctx, L, X, Y, zp, B, Th, Fw);
-#ifdef ALSEP_EXPERIMENTS
-                if (conv_mny_enabled() & 1) return launch_conv_mny<2>(ctx, L, X, Y, zp, B, Th, Fw);
-                return launch_conv_big<2>(ctx, L, X, Y, zp, B, Th, Fw);
-#else
-                break;
-#endif
-            case 3:                                          // 8 VGPRs spill, outside the MFMA loops (ALSEP_CONV_BIG3=0: plain kernel)
-#ifdef ALSEP_EXPERIMENTS
-                if (conv_mny_enabled() & 2) return launch_conv_mny<3>(ctx, L, X, Y, zp, B, Th, Fw);
-#endif
-                if (conv_big3_enabled()) return launch_conv_big<3>(ctx, L, X, Y, zp, B, Th, Fw);
-                break;
-            default: break;                                  // NY = 4 spills heavily at 2 waves/SIMD with ROCm 7.2
-        }
+        (conv_big_enabled() >= 2 || B * (Th / 8) * (Fw / 64) >= 96)) {
+        if (L.cout == 96 && conv_mq_enabled()) return launch_conv_mq(ctx, L, X, Y, zp, B, Th, Fw);
+        if (L.cout == 144 && conv_big3_enabled()) return launch_conv_big3(ctx, L, X, Y, zp, B, Th, Fw);
     }
-#ifdef ALSEP_EXPERIMENTS
-    if (conv_pipe_enabled() && Th % 4 == 0 && Fw % 64 == 0 && L.cin == L.cout &&
-        (conv_pipe_enabled() >= 2 || B * (Th / 4) * (Fw / 64) >= 128)) {   // =2: no minimum tile count (tests)
-        switch (L.cout / 48) {
-            case 2: return launch_conv_pipe<2>(ctx, L, X, Y, zp, B, Th, Fw);
-            case 3: return launch_conv_pipe<3>(ctx, L, X, Y, zp, B, Th, Fw);
-            default: break;                                  // NY = 4 spills registers with ROCm 7.2: stays on the plain kernel
-        }
-    }
-#endif
     if (Fw >= 64 && Fw % 64 == 0) return launch_conv_dma<64>(ctx, L, X, Y, zp, B, Th, Fw);
     if (Fw >= 32) return launch_conv_dma<32>(ctx, L, X, Y, zp, B, Th, Fw);
     return launch_conv_dma<16>(ctx, L, X, Y, zp, B, Th, Fw);
@@ -3932,7 +3409,7 @@ int run_conv(alsep_ctx* ctx, const ConvLayer& L, const T* X, T* Y, int64_t B, in
 }
 
 int pix_stream_enabled() {
-    static const int v = [] { const char* e = getenv("ALSEP_PIX_STREAM"); return e ? atoi(e) : 1; }();
+    static const int v = env_int("ALSEP_PIX_STREAM", 1);
     return v;
 }
 // ALSEP_PIX_PIPE: 1 (default) = the ds / us of the middle levels run on ds_pipe_kernel / us_pipe_kernel for the instances in
@@ -3942,11 +3419,11 @@ int pix_stream_enabled() {
 enum { kPixPipeDs96 = 1, kPixPipeDs144 = 2, kPixPipeUs192 = 4, kPixPipeUs144 = 8 };
 constexpr int kPixPipeRouted = kPixPipeDs96 | kPixPipeDs144 | kPixPipeUs192 | kPixPipeUs144;
 bool pix_pipe_routed(int kind) {
-    static const int v = [] { const char* e = getenv("ALSEP_PIX_PIPE"); return e ? atoi(e) : 1; }();
+    static const int v = env_int("ALSEP_PIX_PIPE", 1);
     return v >= 2 || (v == 1 && (kPixPipeRouted & kind));
 }
 unsigned pix_pipe_grid(alsep_ctx* ctx, int64_t ntile) {     // more than 128 KiB of LDS: one workgroup per CU
-    static const int cap = [] { const char* e = getenv("ALSEP_PIX_PIPE_GRID"); return e ? atoi(e) : 0; }();
+    static const int cap = env_int("ALSEP_PIX_PIPE_GRID", 0);
     int64_t grid = device_cu_count(ctx);
     if (cap > 0 && cap < grid) grid = cap;
     return (unsigned)std::min<int64_t>(grid, ntile);
@@ -4100,7 +3577,7 @@ int run_pix(alsep_ctx* ctx, const GemmLayer& L, const T* X, T* Y, const T* skip,
 // ALSEP_TDF_WIDE: 0 = 128-row kernel only; 1 (default) = wide kernel where M % 192 == 0, 384 rows per workgroup for a
 // first linear whose whole M is 384; 4 / 8 = force 192 / 384 rows wherever M allows (experiments, tests)
 int tdf_wide_mode() {
-    static const int v = [] { const char* e = getenv("ALSEP_TDF_WIDE"); return e ? atoi(e) : 1; }();
+    static const int v = env_int("ALSEP_TDF_WIDE", 1);
     return v;
 }
 // The final 1x1 convolution of a forward, offered to the last residual TDF launch (run_block's `fin`): the launcher that
@@ -4115,7 +3592,7 @@ struct FinalFold {
 // ALSEP_TDF_FINAL: 1 (default) = fold the final 1x1 conv into the last residual TDF launch where the wide 192-row kernel
 // serves it and C == 48; 0 = always the separate final_conv_kernel
 int tdf_final_mode() {
-    static const int v = [] { const char* e = getenv("ALSEP_TDF_FINAL"); return e ? atoi(e) : 1; }();
+    static const int v = env_int("ALSEP_TDF_FINAL", 1);
     return v;
 }
 // ALSEP_TDF_PERSIST: 1 (default) = the residual linear of levels 0 and 1 runs on tdf_bf16_persist_kernel for the launch kinds
@@ -4125,7 +3602,7 @@ int tdf_final_mode() {
 enum { kTdfPersistK384 = 1, kTdfPersistK192 = 2, kTdfPersistFinal = 4 };
 constexpr int kTdfPersistRouted = kTdfPersistK384 | kTdfPersistK192 | kTdfPersistFinal;
 int tdf_persist_mode() {
-    static const int v = [] { const char* e = getenv("ALSEP_TDF_PERSIST"); return e ? atoi(e) : 1; }();
+    static const int v = env_int("ALSEP_TDF_PERSIST", 1);
     return v;
 }
 template <int NT, bool FINAL>
@@ -4142,7 +3619,7 @@ void launch_tdf_persist_inst(alsep_ctx* ctx, hipError_t& attr, unsigned grid, co
 // caller: R != nullptr, M % 384 == 0, K 384 or 192, C 48 or 96, nunits % 4 == 0, inside its ProfScope; fin only where C == 48
 int launch_tdf_persist(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* R, int64_t nunits, int C,
                        FinalFold* fin) {
-    static const int cap = [] { const char* e = getenv("ALSEP_TDF_PERSIST_GRID"); return e ? atoi(e) : 0; }();
+    static const int cap = env_int("ALSEP_TDF_PERSIST_GRID", 0);
     const int64_t nitems = nunits / TdfPersist::UN;
     int64_t grid = device_cu_count(ctx);                             // 156.75 KiB of LDS: one workgroup per CU
     if (cap > 0 && cap < grid) grid = cap;
@@ -4169,12 +3646,12 @@ int launch_tdf_wide(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t*
     const int64_t gx = ceil_div64(nunits, Tc::UN);
     if (gx > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "tdf: too many column tiles");
     const float* bias = L.has_bias ? (const float*)L.bias.p : nullptr;
-    static const int yfast = [] { const char* e = getenv("ALSEP_TDF_YFAST"); return e ? atoi(e) : 1; }();
+    static const int yfast = env_int("ALSEP_TDF_YFAST", 1);
     const int nrb = L.M / Tc::BM;
     const int nyb = (yfast && nrb > 1 && gx % 8 == 0 && gx * nrb <= 0x7fffffff) ? nrb : 0;
     const dim3 grid = nyb ? dim3((unsigned)(gx * nrb)) : dim3((unsigned)gx, nrb);
     ProfScope prof(ctx, ALSEP_PROF_TDF);
-    static const int rpf = [] { const char* e = getenv("ALSEP_TDF_RPF"); return e ? atoi(e) : 2; }();
+    static const int rpf = env_int("ALSEP_TDF_RPF", 2);
     const bool fold = WM == 4 && R && rpf != 0 && fin && C == Tc::UC && tdf_final_mode();
     if (WM == 4 && R && rpf != 0 && tdf_wide_mode() == 1 && L.M % TdfPersist::BM == 0 && (C == Tc::UC || C == 2 * Tc::UC) &&
         (L.K == 384 || L.K == 192)) {

@@ -217,7 +217,7 @@ nn_conv2d_tiled_kernel(const float* __restrict__ x, const float* __restrict__ w,
 
 // the tiled kernel applies when a K-slice stays inside one tap and the rows are 16-byte aligned
 static bool conv_tiled_ok(const float* x, const float* w, int Cin, int Cout, int64_t npix) {
-    static const int on = [] { const char* e = getenv("ALSEP_NN_CONV_TILED"); return e ? atoi(e) : 1; }();
+    static const int on = env_int("ALSEP_NN_CONV_TILED", 1);
     return on && Cin % kCvBK == 0 && Cout % 4 == 0 && npix >= 64 && (((uintptr_t)x | (uintptr_t)w) & 15) == 0;
 }
 static void launch_conv_tiled(alsep_ctx* ctx, const float* x, const float* w, const float* scale, const float* shift, float* y, int64_t npix,

@@ -48,9 +48,6 @@ typedef struct alsep_plan alsep_plan;     /* STFT geometry + twiddle/envelope ta
 typedef struct alsep_net alsep_net;       /* packed TFC-TDF U-Net weights */
 
 int alsep_abi_version(void);
-/* 1 when the library was compiled with -DALSEP_EXPERIMENTS (timing-experiment switches and superseded kernel variants present);
- * the product build returns 0: no environment variable can then change what is computed. */
-int alsep_experiments_enabled(void);
 
 /* ctx: replaces device selection at modules/separator/stem_separator.py:99-100. */
 int alsep_create(int device_id, void* hip_stream, alsep_ctx** out);

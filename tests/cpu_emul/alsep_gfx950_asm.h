@@ -52,7 +52,6 @@ template <int N>
 static inline void lds_wait_n() {}
 static inline void sched_fence() {}
 static inline unsigned long long clock_cycles() { return 0; }
-static inline unsigned long long clock_100mhz() { return 0; }
 
 template <typename T>
 static inline void keep_vgprs_live(const T&) {}

@@ -30,17 +30,10 @@ np.save(sys.argv[1], np.stack(outs))
 """
 
 
-def experiments() -> bool:
-    """True when libalsep.so was compiled with -DALSEP_EXPERIMENTS: only then do the switches of the superseded kernels (PIPE, MNY,
-    BIG_SWP, MQ_PRIO, the NY = 2 big-tile kernel) select anything; the product build ignores them and their cases are skipped."""
-    from audiolab_amd import _lib
-    return bool(_lib.get_lib().alsep_experiments_enabled())
-
-
 def run_mode(mode, path, **extra):
-    regw, pipe, big = mode
+    regw, big = mode
     # ALSEP_CONV_MQ=0 unless asked for: the default level-1 kernel sums in another order (not bit-identical with the kernels compared here)
-    env = dict(os.environ, ALSEP_CONV_REGW=str(regw), ALSEP_CONV_PIPE=str(pipe), ALSEP_CONV_BIG=str(big))
+    env = dict(os.environ, ALSEP_CONV_REGW=str(regw), ALSEP_CONV_BIG=str(big))
     env.update({"ALSEP_CONV_MQ": "0", "ALSEP_CONV_M0": "0", **extra})
     r = subprocess.run([sys.executable, "-c", SCRIPT % {"root": ROOT}, path], env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -48,21 +41,18 @@ def run_mode(mode, path, **extra):
 
 
 def test_persistent_conv_bit_identical(tmp_path):
-    base = run_mode((0, 0, 0), str(tmp_path / "m0.npy"))     # plain LDS-DMA kernel everywhere
+    base = run_mode((0, 0), str(tmp_path / "m0.npy"))        # plain LDS-DMA kernel everywhere
     assert np.isfinite(base).all() and np.abs(base).max() > 1e-3
-    modes = [(1, 0, 0), (2, 0, 0), (3, 0, 0), (1, 0, 1), (0, 0, 2)]                # register-weight / big-tile (NY = 3; NY = 2 in experiments builds)
-    if experiments():
-        modes += [(0, 1, 0), (1, 1, 0)]                                             # software-pipelined plain kernel
-    for mode in modes:
-        got = run_mode(mode, str(tmp_path / ("m%d%d%d.npy" % mode)))
-        assert np.array_equal(base, got), f"REGW,PIPE,BIG={mode}: max diff {np.abs(base - got).max()}"
+    for mode in [(1, 0), (2, 0), (3, 0), (1, 1), (0, 2)]:    # register-weight / big-tile (NY = 3)
+        got = run_mode(mode, str(tmp_path / ("m%d%d.npy" % mode)))
+        assert np.array_equal(base, got), f"REGW,BIG={mode}: max diff {np.abs(base - got).max()}"
 
 
 def test_streaming_ds_us_match_tile_gemm(tmp_path):
     """The register-weight streaming ds / us kernels (48<->96, 96<->144 and 144<->192 channels) against the generic tile GEMM on the
     same layers: same bf16 MFMA and the same k order, so the results must agree bit for bit."""
-    base = run_mode((1, 0, 1), str(tmp_path / "s0.npy"), ALSEP_PIX_STREAM="0")
-    got = run_mode((1, 0, 1), str(tmp_path / "s1.npy"), ALSEP_PIX_STREAM="1")
+    base = run_mode((1, 1), str(tmp_path / "s0.npy"), ALSEP_PIX_STREAM="0")
+    got = run_mode((1, 1), str(tmp_path / "s1.npy"), ALSEP_PIX_STREAM="1")
     assert np.isfinite(base).all() and np.abs(base).max() > 1e-3
     assert np.array_equal(base, got), f"max diff {np.abs(base - got).max()} (peak {np.abs(base).max()})"
 
@@ -71,20 +61,17 @@ def test_dispatch_orders_and_prefetch_bit_identical(tmp_path):
     """XCD-local dispatch orders (plain conv: ALSEP_CONV_NYFAST, wide TDF: ALSEP_TDF_YFAST), the NY = 3 big-tile conv
     (ALSEP_CONV_BIG3) and the residual prefetch of the wide TDF epilogue (ALSEP_TDF_RPF) only change WHICH workgroup
     computes a tile or when a row is loaded -- every switch off must reproduce the default bit for bit."""
-    base = run_mode((1, 0, 1), str(tmp_path / "d0.npy"))
+    base = run_mode((1, 1), str(tmp_path / "d0.npy"))
     assert np.isfinite(base).all() and np.abs(base).max() > 1e-3
     cases = [dict(ALSEP_CONV_NYFAST="0"), dict(ALSEP_TDF_YFAST="0"), dict(ALSEP_CONV_BIG3="0"), dict(ALSEP_TDF_RPF="0"), dict(ALSEP_CONV_M0="2"),
              dict(ALSEP_CONV_NYFAST="0", ALSEP_TDF_YFAST="0", ALSEP_CONV_BIG3="0", ALSEP_TDF_RPF="0")]
-    if experiments():                                         # software-pipelined k-loop also at NY = 3, merged kernel
-        cases += [dict(ALSEP_CONV_BIG_SWP="2"), dict(ALSEP_CONV_MNY="3")]
     for extra in cases:
-        got = run_mode((1, 0, 1), str(tmp_path / "d1.npy"), **extra)
+        got = run_mode((1, 1), str(tmp_path / "d1.npy"), **extra)
         assert np.array_equal(base, got), f"{extra}: max diff {np.abs(base - got).max()}"
     # the fully double-buffered level-1 kernel sums a layer's products in another order (32-channel chunks): equal up to flipped bf16
     # roundings (measured 4.5e-3 relative L2 after three blocks), and deterministic -- a race in its LDS-DMA rings would not be
-    for prio in (("0", "1") if experiments() else ("0",)):
-        a = run_mode((1, 0, 1), str(tmp_path / "q0.npy"), ALSEP_CONV_MQ="1", ALSEP_CONV_MNY="0", ALSEP_CONV_MQ_PRIO=prio)
-        b = run_mode((1, 0, 1), str(tmp_path / "q1.npy"), ALSEP_CONV_MQ="1", ALSEP_CONV_MNY="0", ALSEP_CONV_MQ_PRIO=prio)
-        assert np.array_equal(a, b), f"mq (prio {prio}) is not deterministic: max diff {np.abs(a - b).max()}"
-        rel = float(np.linalg.norm(a - base) / np.linalg.norm(base))
-        assert rel < 2e-2, f"mq (prio {prio}) vs the 48-channel kernels: rel L2 {rel:.3e}"
+    a = run_mode((1, 1), str(tmp_path / "q0.npy"), ALSEP_CONV_MQ="1")
+    b = run_mode((1, 1), str(tmp_path / "q1.npy"), ALSEP_CONV_MQ="1")
+    assert np.array_equal(a, b), f"mq is not deterministic: max diff {np.abs(a - b).max()}"
+    rel = float(np.linalg.norm(a - base) / np.linalg.norm(base))
+    assert rel < 2e-2, f"mq vs the 48-channel kernels: rel L2 {rel:.3e}"
