@@ -21,6 +21,7 @@ PROF_CONV3X3, PROF_CONV3X3_SMALL, PROF_TDF, PROF_PIX, PROF_POINTWISE, PROF_STFT,
 PROF_CONV3X3_REGW, PROF_CONV3X3_PIPE, PROF_CONV3X3_BIG, PROF_CONV3X3_BIG3 = 8, 9, 10, 11
 PROF_NN_GEMM, PROF_NN_CONV, PROF_NN_GEMM_H, PROF_NN_ATTN_H, PROF_NN_CONV_H, PROF_NN_DCONV_H, PROF_NN_NORM_H = 12, 13, 14, 15, 16, 17, 18
 PROF_NN_LSTM, PROF_NN_LOCALSTATE = 19, 20
+PROF_PITCH_ANALYSIS, PROF_PITCH_RECURRENCE, PROF_PITCH_SYNTHESIS, PROF_PITCH_RESAMPLE = 21, 22, 23, 24
 LAYOUT_REF, LAYOUT_NHWC = 0, 1
 ABI_VERSION = 1
 
@@ -199,6 +200,10 @@ _SIGNATURES = {
     "alsep_reverb_apply_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
     "alsep_reverb_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int,
                                      C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "alsep_pitch_shift_frames": (C.c_int64, [C.c_int64, C.c_int, C.c_double]),
+    "alsep_pitch_shift_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_double]),
+    "alsep_pitch_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                    C.c_void_p, C.c_int64]),
     "alsep_mix_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MixStem), C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
                                 C.c_void_p]),
     "alsep_mix_power_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),

@@ -699,3 +699,5 @@ extern "C" int alsep_reverb_envelope_db(alsep_ctx* ctx, const float* x, int c, i
     ALSEP_LAUNCH_CHECK(ctx, "envelope_db_kernel");
     return ALSEP_OK;
 }
+
+#include "pitch.h"

@@ -13,8 +13,13 @@ The mixdown itself -- pydub's overlay / normalize / dBFS match / apply_gain in t
 
 Departures from the reference:
   * lengths are sample-exact; pydub slices by milliseconds;
-  * a non-zero ``pitch_shift`` with a stem that is not a ``(Cloned)`` one raises NotImplementedError before any work: the reference shells
-    out to ffmpeg's rubberband filter (util/audio_track.py), which is not built;
+  * a non-zero ``pitch_shift`` with a stem that is not a ``(Cloned)`` one raises NotImplementedError before any work while the class
+    attribute ``pitch_shifter`` is ``"error"``, the default: the reference shells out to ffmpeg's rubberband filter (util/audio_track.py),
+    which is not built.  With ``Merge.pitch_shifter = "vocoder"`` every such stem is shifted on the GPU by the project's own phase-locked
+    vocoder (audiolab_amd/pitch.py; parity unpinned: no transient handling, channels shifted independently, not rubberband's quality),
+    after the re-reverb step where that applies, and enters the mix from device memory with source width 16 -- the reference's ffmpeg call
+    writes pcm_s16le (util/audio_track.py:642, 678); the ``...(Re-Reverb).wav`` file stays the unshifted reverb output, no other file is
+    written, ``(Cloned)`` stems pass through untouched (Clone shifted the voice already);
   * a ``src_file`` that is not a WAV goes through ``ensure_wav`` (one ffmpeg transcode) before its loudness is read;
   * stems of differing sample rates -- the default chain's case: Separate writes 44.1 kHz, a cloned voice comes at the model's 40 or
     48 kHz -- raise ValueError while the class attribute ``mixed_rates`` is ``"error"``, the default; with ``Merge.mixed_rates = "ratecv"``
@@ -27,7 +32,7 @@ import logging
 import os
 from typing import Any, Dict, List
 
-from audiolab_amd import merge, reverb, wavio
+from audiolab_amd import merge, pitch, reverb, wavio
 from audiolab_amd.separator.stem_separator import _call_progress, ensure_wav
 from audiolab_amd.util.data_classes import ProjectFiles
 from audiolab_amd.wrappers.base_wrapper import BaseWrapper, TypedInput
@@ -77,6 +82,9 @@ class Merge(BaseWrapper):
     ctx = None
     # stems of differing sample rates: "error" (ValueError) or "ratecv" (resampled as pydub's overlay does); not a kwarg of the reference
     mixed_rates = "error"
+    # a non-zero pitch_shift with stems that are not (Cloned): "error" (NotImplementedError) or "vocoder" (audiolab_amd/pitch.py); not a kwarg
+    # of the reference
+    pitch_shifter = "error"
 
     def process_audio(self, pj_inputs: List[ProjectFiles], callback=None, **kwargs: Dict[str, Any]) -> List[ProjectFiles]:
         pj_outputs = []
@@ -91,8 +99,11 @@ class Merge(BaseWrapper):
                 output_folder = os.path.join(project.project_dir, "merged")
                 os.makedirs(output_folder, exist_ok=True)
                 inputs, _ = self.filter_inputs(project, "audio")
-                if pitch_shift != 0 and any("(Cloned)" not in p for p in inputs):                            # :125-127
-                    raise NotImplementedError("Merge: pitch_shift needs ffmpeg's rubberband filter, which this build does not have")
+                if self.pitch_shifter not in ("error", "vocoder"):
+                    raise ValueError(f"Merge.pitch_shifter is {self.pitch_shifter!r}; 'error' or 'vocoder'")
+                if pitch_shift != 0 and self.pitch_shifter == "error" and any("(Cloned)" not in p for p in inputs):   # :125-127
+                    raise NotImplementedError("Merge: pitch_shift needs ffmpeg's rubberband filter, which this build does not have "
+                                              "(Merge.pitch_shifter = 'vocoder' shifts with the project's own phase vocoder)")
                 ir_file = os.path.join(project.project_dir, "stems", "impulse_response.ir")
 
                 new_inputs = []
@@ -104,9 +115,14 @@ class Merge(BaseWrapper):
                         stem_name, ext = os.path.splitext(os.path.basename(stem_path))
                         src_name = stem_name.replace("(Vocals)", "")
                         reverb_stem_path = os.path.join(project.project_dir, "stems", f"{stem_name}(Re-Reverb){ext}")
-                        new_inputs.append(self._re_reverb(stem_path, ir_file, reverb_stem_path))
+                        stem = self._re_reverb(stem_path, ir_file, reverb_stem_path)
+                        shift_from = reverb_stem_path                # the reference shifts what it reads back from that file
                     else:
-                        new_inputs.append(stem_path)
+                        stem = shift_from = stem_path
+                    if pitch_shift != 0 and "(Cloned)" not in stem_path:                                     # :125-127
+                        logger.info(f"Shifting pitch of {os.path.basename(stem_path)} by {pitch_shift} semitones")
+                        stem = self._shift(shift_from, pitch_shift)
+                    new_inputs.append(stem)
 
                 name_str = ""                                                                                # :137-141
                 if selected_voice is not None and selected_voice != "":
@@ -137,3 +153,9 @@ class Merge(BaseWrapper):
         wet = reverb.apply_reverb_array(audio, params["impulse_response"], int(params["pre_delay"] * sr), reverb.WET_GAIN, ctx=self.ctx)
         wavio.write_wav(out_path, wet.cpu().numpy(), sr, subtype="PCM_16")
         return wet, sr, 16
+
+    def _shift(self, stem_path: str, pitch_shift):
+        """util/audio_track.py:603-694 on the device: the shifted stem as a device signal with source width 16, the pcm_s16le the
+        reference's ffmpeg call hands back (:642, :678)"""
+        audio, sr = wavio.read_wav(stem_path)
+        return pitch.shift_pitch_array(audio, pitch_shift, ctx=self.ctx), sr, 16

@@ -78,7 +78,11 @@ enum {
     ALSEP_PROF_NN_DCONV_H = 17,  /* nn_dconv_h_kernel (f16 MFMA convolution of HTDemucs' half-precision mode) */
     ALSEP_PROF_NN_NORM_H = 18,   /* nn_norm_h_* (GroupNorm / LayerNorm to half: statistics, final, apply) */
     ALSEP_PROF_NN_LSTM = 19,     /* nn_lstm_kernel (the recurrence of HDemucs' BLSTM) */
-    ALSEP_PROF_NN_LOCALSTATE = 20 /* nn_localstate_softmax_kernel (HDemucs' LocalState bias / mask / softmax) */
+    ALSEP_PROF_NN_LOCALSTATE = 20,/* nn_localstate_softmax_kernel (HDemucs' LocalState bias / mask / softmax) */
+    ALSEP_PROF_PITCH_ANALYSIS = 21,  /* alsep_pitch_shift: gather, forward transforms, polar form, peaks / owners (pv_lock_kernel) */
+    ALSEP_PROF_PITCH_RECURRENCE = 22,/* pv_recurrence_kernel */
+    ALSEP_PROF_PITCH_SYNTHESIS = 23, /* spectrum, inverse transforms, overlap-add */
+    ALSEP_PROF_PITCH_RESAMPLE = 24   /* pv_resample_kernel */
 };
 int alsep_profile_begin(alsep_ctx* ctx, int category);
 int alsep_profile_end(alsep_ctx* ctx, double* total_ms, int64_t* launches);
@@ -515,6 +519,18 @@ int alsep_reverb_apply_block_log2(int64_t n_ir, int log2_block);              /*
 int64_t alsep_reverb_apply_workspace_bytes(int64_t n_ir, int log2_block, int blocks_per_batch);   /* -1 for a bad geometry */
 int alsep_reverb_apply(alsep_ctx* ctx, const float* dry, int channels, int64_t n, int64_t ld, const double* ir, int64_t n_ir,
                        int64_t pre_delay_samples, double wet_gain, int log2_block, float* out, int64_t ld_out, void* ws, int64_t ws_bytes);
+
+/* ---- pitch shifting of a stem by `ratio` = 2^(semitones / 12), 1/4 <= ratio <= 4: the "transpose the song" step of wrappers/merge.py:125-127
+ * (util/audio_track.py:603-694 shells out to ffmpeg's rubberband filter there; this is the project's own shifter, parity unpinned).  A phase
+ * vocoder with identity phase locking (n_fft a power of two, 256 .. 8192, synthesis hop n_fft / 4, analysis hop n_fft / (4 ratio), periodic
+ * Hann) stretches x by `ratio`, a Kaiser-windowed sinc (64 zero crossings, beta 14.7697, roll-off 0.9476) resamples the result back to n
+ * samples; DESIGN section 4c has the arithmetic.  float32 [channels][n] tensors with row strides ld / ld_out, channels independent; double
+ * precision on the device, one rounding to float32.  Frames travel in batches of frames_per_batch >= 4: the workspace depends on the batch,
+ * not on n, and the result does not depend on the batch by a bit.  out must not overlap x. */
+int64_t alsep_pitch_shift_frames(int64_t n, int n_fft, double ratio);         /* analysis frames U = ceil(n ratio / (n_fft / 4)) + 1; -1: bad geometry */
+int64_t alsep_pitch_shift_workspace_bytes(int channels, int n_fft, int frames_per_batch, double ratio);   /* -1 for a bad geometry */
+int alsep_pitch_shift(alsep_ctx* ctx, const float* x, int channels, int64_t n, int64_t ld, double ratio, int n_fft, int frames_per_batch,
+                      float* out, int64_t ld_out, void* ws, int64_t ws_bytes);
 
 /* ---- stem mixdown with loudness matching: replaces the pydub calls of wrappers/merge.py:15-45,146-151 (AudioSegment.overlay,
  * effects.normalize, .dBFS, .apply_gain), i.e. audioop.add / max / rms / mul, on the signed integer grid of `bits` (16 or 32) with
