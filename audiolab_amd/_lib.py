@@ -22,6 +22,7 @@ PROF_CONV3X3_REGW, PROF_CONV3X3_PIPE, PROF_CONV3X3_BIG, PROF_CONV3X3_BIG3 = 8, 9
 PROF_NN_GEMM, PROF_NN_CONV, PROF_NN_GEMM_H, PROF_NN_ATTN_H, PROF_NN_CONV_H, PROF_NN_DCONV_H, PROF_NN_NORM_H = 12, 13, 14, 15, 16, 17, 18
 PROF_NN_LSTM, PROF_NN_LOCALSTATE = 19, 20
 PROF_PITCH_ANALYSIS, PROF_PITCH_RECURRENCE, PROF_PITCH_SYNTHESIS, PROF_PITCH_RESAMPLE = 21, 22, 23, 24
+PROF_COMPARE_RESAMPLE, PROF_COMPARE_RMS, PROF_COMPARE_WAVE, PROF_COMPARE_SPECTRA, PROF_COMPARE_REDUCE = 25, 26, 27, 28, 29
 LAYOUT_REF, LAYOUT_NHWC = 0, 1
 ABI_VERSION = 1
 
@@ -204,6 +205,17 @@ _SIGNATURES = {
     "alsep_pitch_shift_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_double]),
     "alsep_pitch_shift": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int64,
                                     C.c_void_p, C.c_int64]),
+    "alsep_resample_fft_f64_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
+    "alsep_resample_fft_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
+                                         C.c_int64]),
+    "alsep_compare_frames": (C.c_int64, [C.c_int64]),
+    "alsep_compare_rms_workspace_bytes": (C.c_int64, []),
+    "alsep_compare_rms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    "alsep_compare_wave": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "alsep_compare_spectra": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "alsep_compare_minmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "alsep_compare_colmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "alsep_mix_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MixStem), C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
                                 C.c_void_p]),
     "alsep_mix_power_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),

@@ -309,8 +309,9 @@ int dft_impl(alsep_ctx* ctx, const cplx* in, cplx* out, int64_t n, double sign, 
 // ---- scipy.signal.resample (Fourier method), what librosa.resample(res_type="scipy") runs: the VR band chain going up (spec_utils.py
 // :427).  Two real rows travel as one complex signal (the operator is real and linear, so the complex-input branch of the scipy routine
 // applied to L + i R resamples both).
+template <typename T>
 __global__ void __launch_bounds__(kRvThreads)
-pack_rows_kernel(const float* __restrict__ a, const float* __restrict__ b, cplx* __restrict__ z, int64_t n) {
+pack_rows_kernel(const T* __restrict__ a, const T* __restrict__ b, cplx* __restrict__ z, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * kRvThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRvThreads)
         z[i] = cplx{(double)a[i], b ? (double)b[i] : 0.0};
 }
@@ -337,11 +338,12 @@ resample_spectrum_kernel(const cplx* __restrict__ X, cplx* __restrict__ Y, int64
     }
 }
 
+template <typename T>
 __global__ void __launch_bounds__(kRvThreads)
-unpack_rows_kernel(const cplx* __restrict__ z, float* __restrict__ a, float* __restrict__ b, int64_t n, double scale) {
+unpack_rows_kernel(const cplx* __restrict__ z, T* __restrict__ a, T* __restrict__ b, int64_t n, double scale) {
     for (int64_t i = (int64_t)blockIdx.x * kRvThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRvThreads) {
-        a[i] = (float)(z[i].x * scale);
-        if (b) b[i] = (float)(z[i].y * scale);
+        a[i] = (T)(z[i].x * scale);
+        if (b) b[i] = (T)(z[i].y * scale);
     }
 }
 
@@ -662,33 +664,49 @@ extern "C" int64_t alsep_resample_fft_workspace_bytes(int64_t n_in, int64_t n_ou
     return resample_fft_points(n_in, n_out) * (int64_t)sizeof(cplx);
 }
 
-// x [rows, n_in] (row stride ldx) -> y [rows, n_out] (row stride ldy), float32; rows in pairs through one complex transform each
-extern "C" int alsep_resample_fft(alsep_ctx* ctx, const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int64_t n_in, int64_t n_out,
-                                  void* ws, int64_t ws_bytes) {
-    ALSEP_ENTER(ctx);
+// x [rows, n_in] (row stride ldx) -> y [rows, n_out] (row stride ldy), float32 or float64 rows; rows in pairs through one complex transform each
+template <typename T>
+static int resample_fft_rows(alsep_ctx* ctx, const char* who, const T* x, int64_t ldx, T* y, int64_t ldy, int64_t rows, int64_t n_in, int64_t n_out,
+                             void* ws, int64_t ws_bytes) {
     if (!ctx || !x || !y || !ws || rows <= 0 || n_in <= 0 || n_out <= 0 || n_in > kMaxPoints || n_out > kMaxPoints || ldx < n_in || ldy < n_out)
-        return alsep_fail(ctx, ALSEP_ERR_ARG, "alsep_resample_fft: bad argument");
-    if (ws_bytes < resample_fft_points(n_in, n_out) * (int64_t)sizeof(cplx)) return alsep_fail(ctx, ALSEP_ERR_ARG, "alsep_resample_fft: workspace too small");
+        return alsep_fail(ctx, ALSEP_ERR_ARG, "%s: bad argument", who);
+    if (ws_bytes < resample_fft_points(n_in, n_out) * (int64_t)sizeof(cplx)) return alsep_fail(ctx, ALSEP_ERR_ARG, "%s: workspace too small", who);
     cplx* z = (cplx*)ws;                 // n_in: packed input
     cplx* X = z + n_in;                  // n_in: its spectrum
     cplx* Y = X + n_in;                  // n_out: resampled spectrum
     cplx* o = Y + n_out;                 // n_out: inverse transform
     cplx* dws = o + n_out;
     for (int64_t r = 0; r < rows; r += 2) {
-        const float* a = x + r * ldx;
-        const float* b = r + 1 < rows ? x + (r + 1) * ldx : nullptr;
-        hipLaunchKernelGGL(pack_rows_kernel, dim3(rv_grid(n_in)), dim3(kRvThreads), 0, ctx->stream, a, b, z, n_in);
+        const T* a = x + r * ldx;
+        const T* b = r + 1 < rows ? x + (r + 1) * ldx : nullptr;
+        hipLaunchKernelGGL(pack_rows_kernel<T>, dim3(rv_grid(n_in)), dim3(kRvThreads), 0, ctx->stream, a, b, z, n_in);
         ALSEP_LAUNCH_CHECK(ctx, "pack_rows_kernel");
         if (int rc = dft_impl(ctx, z, X, n_in, -1.0, dws)) return rc;
         hipLaunchKernelGGL(resample_spectrum_kernel, dim3(rv_grid(n_out)), dim3(kRvThreads), 0, ctx->stream, X, Y, n_in, n_out);
         ALSEP_LAUNCH_CHECK(ctx, "resample_spectrum_kernel");
         if (int rc = dft_impl(ctx, Y, o, n_out, +1.0, dws)) return rc;
         // ifft (1 / n_out) times n_out / n_in
-        hipLaunchKernelGGL(unpack_rows_kernel, dim3(rv_grid(n_out)), dim3(kRvThreads), 0, ctx->stream, o, y + r * ldy,
-                           r + 1 < rows ? y + (r + 1) * ldy : nullptr, n_out, 1.0 / (double)n_in);
+        hipLaunchKernelGGL(unpack_rows_kernel<T>, dim3(rv_grid(n_out)), dim3(kRvThreads), 0, ctx->stream, o, y + r * ldy,
+                           r + 1 < rows ? y + (r + 1) * ldy : (T*)nullptr, n_out, 1.0 / (double)n_in);
         ALSEP_LAUNCH_CHECK(ctx, "unpack_rows_kernel");
     }
     return ALSEP_OK;
+}
+
+extern "C" int alsep_resample_fft(alsep_ctx* ctx, const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int64_t n_in, int64_t n_out,
+                                  void* ws, int64_t ws_bytes) {
+    ALSEP_ENTER(ctx);
+    return resample_fft_rows<float>(ctx, "alsep_resample_fft", x, ldx, y, ldy, rows, n_in, n_out, ws, ws_bytes);
+}
+
+// the same with float64 rows (the Compare chain, compare.h): nothing is rounded to single precision on the way
+extern "C" int64_t alsep_resample_fft_f64_workspace_bytes(int64_t n_in, int64_t n_out) { return alsep_resample_fft_workspace_bytes(n_in, n_out); }
+
+extern "C" int alsep_resample_fft_f64(alsep_ctx* ctx, const double* x, int64_t ldx, double* y, int64_t ldy, int64_t rows, int64_t n_in,
+                                      int64_t n_out, void* ws, int64_t ws_bytes) {
+    ALSEP_ENTER(ctx);
+    ProfScope prof(ctx, ALSEP_PROF_COMPARE_RESAMPLE);
+    return resample_fft_rows<double>(ctx, "alsep_resample_fft_f64", x, ldx, y, ldy, rows, n_in, n_out, ws, ws_bytes);
 }
 
 // the decay curve estimate_rt60 fits (reverb.py:74-81), float32 as the reference computes it: x [C, n] -> out [n]
@@ -701,3 +719,4 @@ extern "C" int alsep_reverb_envelope_db(alsep_ctx* ctx, const float* x, int c, i
 }
 
 #include "pitch.h"
+#include "compare.h"

@@ -74,6 +74,28 @@ def read_wav(path: str) -> Tuple[np.ndarray, int]:
     return np.ascontiguousarray(x[: n * ch].reshape(n, ch).T), sr
 
 
+def read_wav_interleaved(path: str) -> Tuple[np.ndarray, int]:
+    """-> (the samples in file order -- interleaved, ``frames * channels`` of them -- as float64 fractions of full scale, frame rate).
+    8 / 16 / 24 / 32-bit PCM: ``v / 2^(bits - 1)``, exact in float64 (8-bit files store ``v + 128``); float samples as they are."""
+    (tag, ch, sr, bits), pcm = _chunks(path)
+    if tag == WAVE_FORMAT_IEEE_FLOAT and bits in (32, 64):
+        width = bits // 8
+        x = np.frombuffer(pcm[: len(pcm) // width * width], dtype="<f4" if bits == 32 else "<f8").astype(np.float64)
+    elif tag == WAVE_FORMAT_PCM and bits == 16:
+        x = np.frombuffer(pcm[: len(pcm) // 2 * 2], dtype="<i2").astype(np.float64) / 32768.0
+    elif tag == WAVE_FORMAT_PCM and bits == 32:
+        x = np.frombuffer(pcm[: len(pcm) // 4 * 4], dtype="<i4").astype(np.float64) / 2147483648.0
+    elif tag == WAVE_FORMAT_PCM and bits == 24:
+        b = np.frombuffer(pcm[: len(pcm) // 3 * 3], dtype=np.uint8).reshape(-1, 3).astype(np.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        x = np.where(v >= 1 << 23, v - (1 << 24), v).astype(np.float64) / 8388608.0
+    elif tag == WAVE_FORMAT_PCM and bits == 8:
+        x = (np.frombuffer(pcm, dtype=np.uint8).astype(np.float64) - 128.0) / 128.0
+    else:
+        raise ValueError(f"{path}: unsupported WAV format tag={tag} bits={bits}")
+    return np.ascontiguousarray(x[: x.size // ch * ch]), sr
+
+
 def write_wav(path: str, audio: np.ndarray, sr: int, subtype: str = "FLOAT") -> None:
     """audio [C, N] (or [N]) -> WAV; subtype "FLOAT" (float32), "PCM_16" or "PCM_32" (round-to-nearest, clipped).  An integer array
     under a PCM subtype holds the samples themselves (already on that grid): they are written as they are, clipped to the range."""

@@ -1,0 +1,1 @@
+from audiolab_amd.wrappers.compare import Compare  # noqa: F401

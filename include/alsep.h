@@ -82,7 +82,12 @@ enum {
     ALSEP_PROF_PITCH_ANALYSIS = 21,  /* alsep_pitch_shift: gather, forward transforms, polar form, peaks / owners (pv_lock_kernel) */
     ALSEP_PROF_PITCH_RECURRENCE = 22,/* pv_recurrence_kernel */
     ALSEP_PROF_PITCH_SYNTHESIS = 23, /* spectrum, inverse transforms, overlap-add */
-    ALSEP_PROF_PITCH_RESAMPLE = 24   /* pv_resample_kernel */
+    ALSEP_PROF_PITCH_RESAMPLE = 24,  /* pv_resample_kernel */
+    ALSEP_PROF_COMPARE_RESAMPLE = 25,/* alsep_resample_fft_f64: pack, the two transforms, the spectrum copy, unpack */
+    ALSEP_PROF_COMPARE_RMS = 26,     /* cmp_sumsq_partial_kernel, cmp_sumsq_final_kernel */
+    ALSEP_PROF_COMPARE_WAVE = 27,    /* cmp_wave_kernel */
+    ALSEP_PROF_COMPARE_SPECTRA = 28, /* cmp_spectra_kernel */
+    ALSEP_PROF_COMPARE_REDUCE = 29   /* cmp_minmax_kernel, cmp_colmax_kernel */
 };
 int alsep_profile_begin(alsep_ctx* ctx, int category);
 int alsep_profile_end(alsep_ctx* ctx, double* total_ms, int64_t* launches);
@@ -152,6 +157,10 @@ int alsep_resample_poly(alsep_ctx* ctx, const float* x, float* y, int64_t rows, 
 int64_t alsep_resample_fft_workspace_bytes(int64_t n_in, int64_t n_out);
 int alsep_resample_fft(alsep_ctx* ctx, const float* x, int64_t ldx, float* y, int64_t ldy, int64_t rows, int64_t n_in, int64_t n_out,
                        void* ws, int64_t ws_bytes);
+/* the same on float64 rows (the Compare chain below): no rounding to single precision on the way */
+int64_t alsep_resample_fft_f64_workspace_bytes(int64_t n_in, int64_t n_out);
+int alsep_resample_fft_f64(alsep_ctx* ctx, const double* x, int64_t ldx, double* y, int64_t ldy, int64_t rows, int64_t n_in, int64_t n_out,
+                           void* ws, int64_t ws_bytes);
 /* zero the lowest nbins bins of a spectrogram in place (MDXSeparator.run_model zeroes bins 0..2). */
 int alsep_zero_low_bins(alsep_ctx* ctx, void* spec, int dtype, int layout, int64_t B, int64_t dim_f, int64_t T,
                         int nbins);
@@ -531,6 +540,30 @@ int64_t alsep_pitch_shift_frames(int64_t n, int n_fft, double ratio);         /*
 int64_t alsep_pitch_shift_workspace_bytes(int channels, int n_fft, int frames_per_batch, double ratio);   /* -1 for a bad geometry */
 int alsep_pitch_shift(alsep_ctx* ctx, const float* x, int channels, int64_t n, int64_t ld, double ratio, int n_fft, int frames_per_batch,
                       float* out, int64_t ld_out, void* ws, int64_t ws_bytes);
+
+/* ---- the arithmetic of the Compare plugin (wrappers/compare.py:92-124, :145, :152): two float64 tracks of n >= 2048 samples at the common
+ * rate, RMS-normalised, their absolute difference, and scipy.signal.stft(x, nperseg=2048, noverlap=1024) of both -- periodic Hann, zero
+ * boundary, padded tail, scaled by 1 / sum(window): F = 1 + ceil(n / 1024) frames, frame f holding the samples [1024 f - 1024, 1024 f + 1024)
+ * -- as 20 log10(S1 + 1e-9) and 20 log10(|S1 - S2| + 1e-9).  Float64 on the device; the decibel arrays are float32 [1025][F].  n <= 2^31. */
+int64_t alsep_compare_frames(int64_t n);                                      /* F, or -1 for n < 2048 or n > 2^31 */
+/* *sumsq_out (device) = the sum of the squares of x[0 .. n) in a reduction order that depends on n alone: the same bits on every run, no
+ * floating-point atomics.  ws: alsep_compare_rms_workspace_bytes() bytes. */
+int64_t alsep_compare_rms_workspace_bytes(void);
+int alsep_compare_rms(alsep_ctx* ctx, const double* x, int64_t n, double* sumsq_out, void* ws, int64_t ws_bytes);
+/* sumsq: device, [2], the sums of squares of x0 and x1 over n samples.  w_i = x_i / rms_i where rms_i = sqrt(sumsq[i] / n) > 1e-9, else
+ * x_i as it is (:96-99); diff = |w0 - w1| (:102).  The outputs overlap nothing. */
+int alsep_compare_wave(alsep_ctx* ctx, const double* x0, const double* x1, int64_t n, const double* sumsq, double* w0, double* w1, double* diff);
+/* window: device, float64 [2048], the periodic Hann window; twiddle: device, interleaved float64 (re, im) [2048], exp(-2 pi i m / 2048);
+ * both computed by the caller on the host.  The two frames of a column go through one 2048-point complex transform in LDS, one workgroup
+ * per frame, at most frames_per_batch frames per launch (0: the default, 65536); the result does not depend on it.  spec1_db, diff_db:
+ * float32 [1025][F]; s1_lin, sd_lin: S1 and |S1 - S2| themselves, float64 [1025][F], or NULL. */
+int alsep_compare_spectra(alsep_ctx* ctx, const double* w0, const double* w1, int64_t n, const double* window, const double* twiddle,
+                          int frames_per_batch, float* spec1_db, float* diff_db, double* s1_lin, double* sd_lin);
+/* Bucket j of `buckets` (1 .. n) holds the samples [floor(j n / buckets), floor((j + 1) n / buckets)): its smallest and largest value with
+ * the first index of each.  All outputs on the device, [buckets]. */
+int alsep_compare_minmax(alsep_ctx* ctx, const double* x, int64_t n, int64_t buckets, double* mn, int64_t* imn, double* mx, int64_t* imx);
+/* in: float32 [1025][frames]; out [1025][buckets] = the largest value of each bin over the frame buckets (same rule, 1 <= buckets <= frames) */
+int alsep_compare_colmax(alsep_ctx* ctx, const float* in, int64_t frames, int64_t buckets, float* out);
 
 /* ---- stem mixdown with loudness matching: replaces the pydub calls of wrappers/merge.py:15-45,146-151 (AudioSegment.overlay,
  * effects.normalize, .dBFS, .apply_gain), i.e. audioop.add / max / rms / mul, on the signed integer grid of `bits` (16 or 32) with
