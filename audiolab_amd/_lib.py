@@ -216,6 +216,29 @@ _SIGNATURES = {
                                         C.c_void_p, C.c_void_p]),
     "alsep_compare_minmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "alsep_compare_colmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "alsep_master_workspace_bytes": (C.c_int64, []),
+    "alsep_master_midside": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64]),
+    "alsep_master_leftright": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64]),
+    "alsep_master_piece_sumsq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_int64]),
+    "alsep_master_peak": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    "alsep_master_spectrum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_double,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "alsep_master_convolve_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int]),
+    "alsep_master_convolve_same": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.c_int,
+                                             C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "alsep_master_slide_max": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "alsep_master_iir_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int]),
+    "alsep_master_iir": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_int64]),
+    "alsep_master_filtfilt_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int]),
+    "alsep_master_filtfilt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_int64]),
+    "alsep_master_rectify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
+    "alsep_master_maximum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "alsep_master_limit_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "alsep_master_pcm24": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64, C.c_void_p]),
     "alsep_mix_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MixStem), C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
                                 C.c_void_p]),
     "alsep_mix_power_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),

@@ -388,8 +388,9 @@ ir_pad_kernel(const double* __restrict__ ir, int64_t n_ir, double scale, cplx* _
 
 // blocks b0 .. b0 + blocks of the channel pair (x0, x1): z[b][p] = x0[s] + i x1[s], s = (b0 + b) S + p - (L - 1); zero outside [0, n)
 // and for a missing second channel
+template <typename T>
 __global__ void __launch_bounds__(kRvThreads)
-ola_gather_kernel(const float* __restrict__ x0, const float* __restrict__ x1, int64_t n, cplx* __restrict__ z, int log2F, int64_t S, int64_t L,
+ola_gather_kernel(const T* __restrict__ x0, const T* __restrict__ x1, int64_t n, cplx* __restrict__ z, int log2F, int64_t S, int64_t L,
                   int64_t b0, int64_t blocks) {
     const int64_t F = (int64_t)1 << log2F, total = blocks << log2F;
     for (int64_t i = (int64_t)blockIdx.x * kRvThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kRvThreads) {
@@ -461,6 +462,61 @@ int ola_block_log2(int64_t n_ir, int log2_block) {
     const int need = log2_ceil(2 * n_ir);
     if (log2_block == 0) return need < 10 ? 10 : need;
     return (log2_block < need || log2_block > 21) ? -1 : log2_block;
+}
+
+// The overlap-save core shared by alsep_reverb_apply and alsep_master_convolve_same (master.h): the workspace holds the filter's spectrum
+// h and two F-point buffers per block of a batch.
+struct OlaPlan {
+    int k;
+    int64_t F, L, S, per_batch;
+    cplx *h, *a, *b;
+};
+
+bool ola_plan(int k, int64_t n_ir, void* ws, int64_t ws_bytes, OlaPlan* p) {
+    p->k = k;
+    p->F = (int64_t)1 << k;
+    p->L = n_ir;
+    p->S = p->F - n_ir + 1;
+    const int64_t fit = ws_bytes / ((int64_t)sizeof(cplx) << k);            // F-point buffers the workspace holds
+    if (fit < 3) return false;
+    p->per_batch = (fit - 1) / 2;
+    p->h = (cplx*)ws;
+    p->a = p->h + p->F;
+    p->b = nullptr;                                                          // set by ola_run, behind the a buffers of its batch
+    return true;
+}
+
+// the filter's spectrum, pre-scaled by scale / F, into plan.h; the ping-pong starts in the buffer that makes the last pass land there
+int ola_ir_spectrum(alsep_ctx* ctx, const OlaPlan& p, const double* ir, double scale) {
+    const int passes = (p.k + 2) / 3;
+    cplx* h0 = passes % 2 == 0 ? p.h : p.a;
+    hipLaunchKernelGGL(ir_pad_kernel, dim3(rv_grid(p.F)), dim3(kRvThreads), 0, ctx->stream, ir, p.L, scale, h0, p.F);
+    ALSEP_LAUNCH_CHECK(ctx, "ir_pad_kernel");
+    cplx* hs = nullptr;
+    if (int rc = fft_pow2(ctx, h0, h0 == p.h ? p.a : p.h, p.k, -1.0, &hs)) return rc;
+    if (hs != p.h) return alsep_fail(ctx, ALSEP_ERR_STATE, "overlap-save: the filter's spectrum landed in the wrong buffer");
+    return ALSEP_OK;
+}
+
+// blocks 0 .. n_blocks of the channel pair (x0, x1) in batches: gather, transform, times h, transform back; finish(y, b0, nb) stores
+// the batch's samples
+template <typename T, typename Finish>
+int ola_run(alsep_ctx* ctx, const OlaPlan& p, const T* x0, const T* x1, int64_t n, int64_t n_blocks, Finish finish) {
+    const int64_t per_batch = p.per_batch > n_blocks ? n_blocks : p.per_batch;
+    cplx* a = p.a;
+    cplx* b = a + per_batch * p.F;
+    for (int64_t b0 = 0; b0 < n_blocks; b0 += per_batch) {
+        const int64_t nb = n_blocks - b0 < per_batch ? n_blocks - b0 : per_batch;
+        hipLaunchKernelGGL(ola_gather_kernel<T>, dim3(rv_grid(nb * p.F)), dim3(kRvThreads), 0, ctx->stream, x0, x1, n, a, p.k, p.S, p.L, b0, nb);
+        ALSEP_LAUNCH_CHECK(ctx, "ola_gather_kernel");
+        cplx *f = nullptr, *y = nullptr;
+        if (int rc = fft_pow2_batched(ctx, a, b, p.k, -1.0, nb, &f)) return rc;
+        hipLaunchKernelGGL(ola_product_kernel, dim3(rv_grid(nb * p.F)), dim3(kRvThreads), 0, ctx->stream, f, p.h, p.k, nb);
+        ALSEP_LAUNCH_CHECK(ctx, "ola_product_kernel");
+        if (int rc = fft_pow2_batched(ctx, f, f == a ? b : a, p.k, +1.0, nb, &y)) return rc;
+        if (int rc = finish((const cplx*)y, b0, nb)) return rc;
+    }
+    return ALSEP_OK;
 }
 
 }  // namespace
@@ -609,47 +665,28 @@ extern "C" int alsep_reverb_apply(alsep_ctx* ctx, const float* dry, int channels
                           (long long)n_ir, (long long)kMaxIrTaps, log2_block);
     const float *dry_end = dry + ((int64_t)(channels - 1) * ld + n), *out_end = out + ((int64_t)(channels - 1) * ld_out + n);
     if (dry < out_end && out < dry_end) return alsep_fail(ctx, ALSEP_ERR_ARG, "alsep_reverb_apply: out overlaps dry");
-    const int64_t F = (int64_t)1 << k, L = n_ir, S = F - L + 1;
-    const int64_t fit = ws_bytes / ((int64_t)sizeof(cplx) << k);            // F-point buffers the workspace holds
-    if (fit < 3) return alsep_fail(ctx, ALSEP_ERR_ARG, "alsep_reverb_apply: workspace too small");
+    OlaPlan plan;
+    if (!ola_plan(k, n_ir, ws, ws_bytes, &plan)) return alsep_fail(ctx, ALSEP_ERR_ARG, "alsep_reverb_apply: workspace too small");
     const int64_t head = pre_delay_samples < n ? pre_delay_samples : n;
-    const int64_t n_blocks = ceil_div64(n - head, S);                       // convolution samples 0 .. n - pre are all that survive the crop
-    int64_t per_batch = (fit - 1) / 2;
-    if (per_batch > n_blocks) per_batch = n_blocks;
+    const int64_t n_blocks = ceil_div64(n - head, plan.S);                  // convolution samples 0 .. n - pre are all that survive the crop
     if (head > 0) {
         hipLaunchKernelGGL(ola_head_kernel, dim3(rv_grid(channels * head)), dim3(kRvThreads), 0, ctx->stream, dry, out, channels, ld, ld_out, head);
         ALSEP_LAUNCH_CHECK(ctx, "ola_head_kernel");
     }
     if (n_blocks == 0) return ALSEP_OK;
-    cplx* h = (cplx*)ws;
-    cplx* a = h + F;
-    cplx* b = a + per_batch * F;
-    // the IR's spectrum, once per call; the ping-pong starts in the buffer that makes the last pass land in h
-    const int passes = (k + 2) / 3;
-    cplx* h0 = passes % 2 == 0 ? h : a;
-    hipLaunchKernelGGL(ir_pad_kernel, dim3(rv_grid(F)), dim3(kRvThreads), 0, ctx->stream, ir, L, 1.0 / (double)F, h0, F);
-    ALSEP_LAUNCH_CHECK(ctx, "ir_pad_kernel");
-    cplx* hs = nullptr;
-    if (int rc = fft_pow2(ctx, h0, h0 == h ? a : h, k, -1.0, &hs)) return rc;
-    if (hs != h) return alsep_fail(ctx, ALSEP_ERR_STATE, "alsep_reverb_apply: spectrum landed in the wrong buffer");
+    if (int rc = ola_ir_spectrum(ctx, plan, ir, 1.0 / (double)plan.F)) return rc;   // once per call
     for (int c = 0; c < channels; c += 2) {
         const float* x0 = dry + (int64_t)c * ld;
         const float* x1 = c + 1 < channels ? x0 + ld : nullptr;
         float* y0 = out + (int64_t)c * ld_out;
         float* y1 = x1 ? y0 + ld_out : nullptr;
-        for (int64_t b0 = 0; b0 < n_blocks; b0 += per_batch) {
-            const int64_t nb = n_blocks - b0 < per_batch ? n_blocks - b0 : per_batch;
-            hipLaunchKernelGGL(ola_gather_kernel, dim3(rv_grid(nb * F)), dim3(kRvThreads), 0, ctx->stream, x0, x1, n, a, k, S, L, b0, nb);
-            ALSEP_LAUNCH_CHECK(ctx, "ola_gather_kernel");
-            cplx *f = nullptr, *y = nullptr;
-            if (int rc = fft_pow2_batched(ctx, a, b, k, -1.0, nb, &f)) return rc;
-            hipLaunchKernelGGL(ola_product_kernel, dim3(rv_grid(nb * F)), dim3(kRvThreads), 0, ctx->stream, f, h, k, nb);
-            ALSEP_LAUNCH_CHECK(ctx, "ola_product_kernel");
-            if (int rc = fft_pow2_batched(ctx, f, f == a ? b : a, k, +1.0, nb, &y)) return rc;
-            hipLaunchKernelGGL(ola_finish_kernel, dim3(rv_grid(nb * S)), dim3(kRvThreads), 0, ctx->stream, y, x0, x1, y0, y1, n, k, S, L,
-                               pre_delay_samples, wet_gain, b0, nb);
+        auto finish = [&](const cplx* y, int64_t b0, int64_t nb) {
+            hipLaunchKernelGGL(ola_finish_kernel, dim3(rv_grid(nb * plan.S)), dim3(kRvThreads), 0, ctx->stream, y, x0, x1, y0, y1, n, plan.k, plan.S,
+                               plan.L, pre_delay_samples, wet_gain, b0, nb);
             ALSEP_LAUNCH_CHECK(ctx, "ola_finish_kernel");
-        }
+            return (int)ALSEP_OK;
+        };
+        if (int rc = ola_run<float>(ctx, plan, x0, x1, n, n_blocks, finish)) return rc;
     }
     return ALSEP_OK;
 }
@@ -720,3 +757,4 @@ extern "C" int alsep_reverb_envelope_db(alsep_ctx* ctx, const float* x, int c, i
 
 #include "pitch.h"
 #include "compare.h"
+#include "master.h"

@@ -98,7 +98,9 @@ def read_wav_interleaved(path: str) -> Tuple[np.ndarray, int]:
 
 def write_wav(path: str, audio: np.ndarray, sr: int, subtype: str = "FLOAT") -> None:
     """audio [C, N] (or [N]) -> WAV; subtype "FLOAT" (float32), "PCM_16" or "PCM_32" (round-to-nearest, clipped).  An integer array
-    under a PCM subtype holds the samples themselves (already on that grid): they are written as they are, clipped to the range."""
+    under a PCM subtype holds the samples themselves (already on that grid): they are written as they are, clipped to the range.
+    "PCM_24": 3-byte samples; floats go through libsndfile's rule for doubles, rint(x * 8388607) clipped to +/-8388607; an integer
+    array must be 32 bits wide or wider (no narrower type holds the 24-bit grid: an int16 array is samples of another width, ValueError)."""
     a = np.asarray(audio)
     if a.ndim == 1:
         a = a[None, :]
@@ -115,6 +117,15 @@ def write_wav(path: str, audio: np.ndarray, sr: int, subtype: str = "FLOAT") -> 
         else:
             grid = np.clip(np.rint(inter.astype(np.float64) * full), -full, full - 1.0)
         payload = grid.astype("<i2" if bits == 16 else "<i4").tobytes()
+    elif subtype == "PCM_24":
+        tag, bits = WAVE_FORMAT_PCM, 24
+        if np.issubdtype(inter.dtype, np.integer) and inter.dtype.itemsize < 4:
+            raise ValueError(f"unsupported subtype {subtype} for {inter.dtype} samples: the 24-bit grid needs a 32-bit integer type or floats")
+        if np.issubdtype(inter.dtype, np.integer):
+            grid = np.clip(inter.astype(np.int64), -(1 << 23), (1 << 23) - 1)
+        else:
+            grid = np.clip(np.rint(inter.astype(np.float64) * 8388607.0), -8388607.0, 8388607.0)
+        payload = np.ascontiguousarray(grid.astype("<i4").reshape(-1).view(np.uint8).reshape(-1, 4)[:, :3]).tobytes()
     else:
         raise ValueError(f"unsupported subtype {subtype}")
     block = ch * bits // 8

@@ -565,6 +565,58 @@ int alsep_compare_minmax(alsep_ctx* ctx, const double* x, int64_t n, int64_t buc
 /* in: float32 [1025][frames]; out [1025][buckets] = the largest value of each bin over the frame buckets (same rule, 1 <= buckets <= frames) */
 int alsep_compare_colmax(alsep_ctx* ctx, const float* in, int64_t frames, int64_t buckets, float* out);
 
+/* ---- reference-track mastering: the arithmetic behind the Remaster plugin (wrappers/remaster.py:67-76 hands both files to the Matchering
+ * library; this is the project's restatement of that published design, parity unpinned: tests/remaster_oracle.py).
+ * Float64 on the device throughout; stereo signals are [2][n] rows with a row stride.  Each step is its own entry point; the host
+ * (audiolab_amd/master.py) chains them and designs the matching FIR from the two averaged spectra.  n <= 2^30.  Reductions have a fixed
+ * order (no floating-point atomics).  ws of the functions without a size function of their own: alsep_master_workspace_bytes(). */
+int64_t alsep_master_workspace_bytes(void);
+/* ms[0] = (L / divisor + R / divisor) / 2, ms[1] = (L / divisor - R / divisor) / 2 */
+int alsep_master_midside(alsep_ctx* ctx, const double* lr, int64_t n, int64_t ld, double divisor, double* ms, int64_t ld_ms);
+/* lr[0] = scale mid + scale side, lr[1] = scale mid - scale side */
+int alsep_master_leftright(alsep_ctx* ctx, const double* ms, int64_t n, int64_t ld_ms, double scale, double* lr, int64_t ld);
+/* sums[j] (device, j < d <= 64) = the sum of the squares of x[j p .. (j + 1) p), or of clip(scale x, -1, 1) when clip != 0; d p <= n */
+int alsep_master_piece_sumsq(alsep_ctx* ctx, const double* x, int64_t n, int d, int64_t p, double scale, int clip, double* sums, void* ws,
+                             int64_t ws_bytes);
+/* *peak (device) = max|x| over rows (1 or 2) of n samples */
+int alsep_master_peak(alsep_ctx* ctx, const double* x, int rows, int64_t n, int64_t ld, double* peak, void* ws, int64_t ws_bytes);
+/* out[0][k], out[1][k], k <= n_fft / 2 (device): the mean of |rfft(frame)| scale / n_fft over the whole n_fft-sample frames of the listed
+ * pieces (HOST array of n_pieces <= 64 piece indices; piece j = samples [j p, (j + 1) p)) of ms[0] and ms[1] -- scipy.signal.stft(pieces,
+ * window="boxcar", nperseg=n_fft, noverlap=0, boundary=None, padded=False), magnitudes averaged.  n_fft: a power of two, 256 .. 8192, <= p;
+ * twiddle: device, interleaved float64 (re, im) [n_fft], exp(-2 pi i m / n_fft), computed by the caller on the host; scale >= 0. */
+int alsep_master_spectrum(alsep_ctx* ctx, const double* ms, int64_t n, int64_t ld_ms, int64_t p, const int32_t* pieces, int n_pieces, int n_fft,
+                          double scale, const double* twiddle, double* out, void* ws, int64_t ws_bytes);
+/* out[c] = scale * scipy.signal.fftconvolve(x[c], fir[c], "same"), c < channels: float64 rows, fir: device float64 [channels][n_fir].  The
+ * overlap-save blocks of alsep_reverb_apply (same block exponent rule, same workspace rule: its size decides how many blocks run side by
+ * side, the result does not depend on it); out must not overlap x. */
+int64_t alsep_master_convolve_workspace_bytes(int64_t n_fir, int log2_block, int blocks_per_batch);
+int alsep_master_convolve_same(alsep_ctx* ctx, const double* x, int channels, int64_t n, int64_t ld, const double* fir, int64_t n_fir, double scale,
+                               int log2_block, double* out, int64_t ld_out, void* ws, int64_t ws_bytes);
+/* centred != 0: out[i] = max x[i - (w - 1) .. i + (w - 1)], scipy.ndimage.maximum_filter1d(x, size=2 w - 1) with its "reflect" edges;
+ * else out[i] = max x[max(0, i - w + 1) .. i].  2 w - 1 <= 8191; ALSEP_ERR_ARG for n < 2 w - 1.  out != x. */
+int alsep_master_slide_max(alsep_ctx* ctx, const double* x, int64_t n, int w, int centred, double* out);
+/* y = scipy.signal.lfilter([b0, b1], [1, a1], x, zi=[zi]) (reverse == 0), or the same filter run over x[::-1] with the result stored back
+ * in x's order.  A scan: recurrences local to chunks of `chunk` samples (0: the default, 4096; at most 8192), a carry pass over the chunk
+ * ends, a correction pass -- three launches.  |a1| <= 1; y != x. */
+int64_t alsep_master_iir_workspace_bytes(int64_t n, int chunk);
+int alsep_master_iir(alsep_ctx* ctx, const double* x, int64_t n, double b0, double b1, double a1, double zi, int reverse, int chunk, double* y,
+                     void* ws, int64_t ws_bytes);
+/* y = scipy.signal.filtfilt([b0, b1], [1, a1], x) with its defaults: odd extension by 6 samples (n >= 7), each pass started from zi times
+ * the first sample it sees; zi = scipy.signal.lfilter_zi(b, a)[0], computed by the caller */
+int64_t alsep_master_filtfilt_workspace_bytes(int64_t n, int chunk);
+int alsep_master_filtfilt(alsep_ctx* ctx, const double* x, int64_t n, double b0, double b1, double a1, double zi, int chunk, double* y, void* ws,
+                          int64_t ws_bytes);
+/* the limiter's front: g = 1 - 1 / rect, rect = max(max(|L|, |R|), threshold) / threshold; *over (device) = 1 when some rect is not
+ * numpy.isclose to 1 (|rect - 1| > 1e-8 + 1e-5), else 0 */
+int alsep_master_rectify(alsep_ctx* ctx, const double* lr, int64_t n, int64_t ld, double threshold, double* g, int32_t* over);
+int alsep_master_maximum(alsep_ctx* ctx, const double* a, const double* b, int64_t n, double* out);   /* out = max(a, b) */
+/* the limiter's back: gain = 1 - max(s_h, g_a, max(h, rel)) (stored when gain != NULL), out = lr * gain, *peak (device) = max|out| */
+int alsep_master_limit_apply(alsep_ctx* ctx, const double* lr, int64_t n, int64_t ld, const double* s_h, const double* g_a, const double* h,
+                             const double* rel, double* out, int64_t ld_out, double* gain, double* peak, void* ws, int64_t ws_bytes);
+/* result = lr / divisor (not lr itself); pcm (device, uint8 [6 n]): 24-bit PCM as libsndfile writes doubles -- rint(result 8388607), ties to
+ * even, clipped to +/-8388607, little-endian 3-byte samples, L R interleaved */
+int alsep_master_pcm24(alsep_ctx* ctx, const double* lr, int64_t n, int64_t ld, double divisor, double* result, int64_t ld_res, uint8_t* pcm);
+
 /* ---- stem mixdown with loudness matching: replaces the pydub calls of wrappers/merge.py:15-45,146-151 (AudioSegment.overlay,
  * effects.normalize, .dBFS, .apply_gain), i.e. audioop.add / max / rms / mul, on the signed integer grid of `bits` (16 or 32) with
  * full scale M = 2^(bits-1).  The mix is int32 [channels][n] (row stride ld) for both widths; channels * n <= 2^31.
