@@ -350,7 +350,9 @@ nn_stats_partial_kernel(const float* __restrict__ x, int64_t per_group, int nb, 
         part[((int64_t)g * nb + blk) * 2 + 1] = q;
     }
 }
-// stats[g] = (mean, rstd or std): mode 0 -> rstd = 1/sqrt(var_biased + eps) (normalisation layers); mode 1 -> unbiased std
+// stats[g] = (mean, rstd or std): mode 0 -> rstd = 1/sqrt(var_biased + eps) (normalisation layers); mode 1 -> unbiased std.
+// stats[2 G + g] = what the float32 mean leaves of the fp64 one: half an ulp of a mean far from zero is many standard deviations of data
+// that varies little around it (mean 50, std 0.01: 2e-4 of the normalised output), so the apply kernels subtract both parts
 __global__ void nn_stats_final_kernel(const double* __restrict__ part, int nb, int64_t per_group, int G, float eps, int mode,
                                       float* __restrict__ stats) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -364,26 +366,28 @@ __global__ void nn_stats_final_kernel(const double* __restrict__ part, int nb, i
     double var = q / n - mean * mean;
     if (var < 0.0) var = 0.0;
     stats[2 * g] = (float)mean;
+    stats[2 * G + g] = (float)(mean - (double)(float)mean);
     if (mode == 0) stats[2 * g + 1] = (float)(1.0 / sqrt(var + (double)eps));
     else stats[2 * g + 1] = (float)sqrt(per_group > 1 ? var * n / (n - 1.0) : 0.0);
 }
-// y = act(((x - mean_g) * rstd_g) * gamma[c] + beta[c]); act 0 none, 3 GELU, 4 GLU (C -> C/2 output channels)
+// y = act(((x - mean_g) * rstd_g) * gamma[c] + beta[c]); act 0 none, 3 GELU, 4 GLU (C -> C/2 output channels); mean_g = stats[2 g] +
+// mean_lo[g], subtracted one after the other
 __global__ void __launch_bounds__(kNnThreads)
 nn_norm_apply_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ gamma,
-                     const float* __restrict__ beta, const float* __restrict__ stats, int64_t n_out, int64_t rows_per_group, int C,
-                     int act) {
+                     const float* __restrict__ beta, const float* __restrict__ stats, const float* __restrict__ mean_lo, int64_t n_out,
+                     int64_t rows_per_group, int C, int act) {
     const int Co = act == 4 ? C / 2 : C;
     for (int64_t i = (int64_t)blockIdx.x * kNnThreads + threadIdx.x; i < n_out; i += (int64_t)gridDim.x * kNnThreads) {
         const int c = (int)(i % Co);
         const int64_t row = i / Co;
         const int64_t g = row / rows_per_group;
-        const float mean = stats[2 * g], rstd = stats[2 * g + 1];
+        const float mean = stats[2 * g], rstd = stats[2 * g + 1], mlo = mean_lo[g];
         const float* xr = x + row * C;
-        float v = (xr[c] - mean) * rstd;
+        float v = ((xr[c] - mean) - mlo) * rstd;
         if (gamma) v = fmaf(v, gamma[c], beta[c]);
         if (act == 3) v = gelu_erf(v);
         else if (act == 4) {
-            float u = (xr[c + Co] - mean) * rstd;
+            float u = ((xr[c + Co] - mean) - mlo) * rstd;
             if (gamma) u = fmaf(u, gamma[c + Co], beta[c + Co]);
             v *= sigmoidf_(u);
         }
@@ -419,15 +423,16 @@ nn_scale_add_kernel(const float* __restrict__ a, const float* __restrict__ b, co
 // arithmetic of the scalar kernels above.
 __global__ void __launch_bounds__(kNnThreads)
 nn_norm_apply4_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta,
-                      const float* __restrict__ stats, unsigned n4, unsigned rows_per_group, int C, int act) {
+                      const float* __restrict__ stats, const float* __restrict__ mean_lo, unsigned n4, unsigned rows_per_group, int C,
+                      int act) {
     const unsigned Co4 = (unsigned)(act == 4 ? C / 2 : C) / 4;
     for (unsigned i = blockIdx.x * kNnThreads + threadIdx.x; i < n4; i += gridDim.x * kNnThreads) {
         const unsigned row = i / Co4, c = (i - row * Co4) * 4, g = row / rows_per_group;
-        const float mean = stats[2 * g], rstd = stats[2 * g + 1];
+        const float mean = stats[2 * g], rstd = stats[2 * g + 1], mlo = mean_lo[g];
         const float* xr = x + (int64_t)row * C + c;
         f32x4 v = *reinterpret_cast<const f32x4*>(xr);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (v[e] - mean) * rstd;
+        for (int e = 0; e < 4; ++e) v[e] = ((v[e] - mean) - mlo) * rstd;
         if (gamma) {
             const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c), bt = *reinterpret_cast<const f32x4*>(beta + c);
 #pragma unroll
@@ -440,7 +445,7 @@ nn_norm_apply4_kernel(const float* __restrict__ x, float* __restrict__ y, const 
             const unsigned Co = Co4 * 4;
             f32x4 u = *reinterpret_cast<const f32x4*>(xr + Co);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) u[e] = (u[e] - mean) * rstd;
+            for (int e = 0; e < 4; ++e) u[e] = ((u[e] - mean) - mlo) * rstd;
             if (gamma) {
                 const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c + Co), bt = *reinterpret_cast<const f32x4*>(beta + c + Co);
 #pragma unroll
@@ -1267,7 +1272,7 @@ static int stats_nb(int64_t per_group, int64_t G) {
 }
 extern "C" int64_t alsep_nn_stats_workspace_bytes(int64_t G, int64_t per_group) {
     if (G <= 0 || per_group <= 0) return -1;
-    return (int64_t)sizeof(double) * 2 * G * stats_nb(per_group, G) + (int64_t)sizeof(float) * 2 * G + 64;
+    return (int64_t)sizeof(double) * 2 * G * stats_nb(per_group, G) + (int64_t)sizeof(float) * 3 * G + 64;
 }
 
 static int run_stats(alsep_ctx* ctx, const float* x, int64_t G, int64_t per_group, float eps, int mode, void* workspace,
@@ -1300,10 +1305,10 @@ extern "C" int alsep_nn_norm(alsep_ctx* ctx, const float* x, float* y, const flo
     if (C % 4 == 0 && Co % 4 == 0 && n_out / 4 < ((int64_t)1 << 31) && R < ((int64_t)1 << 31) &&
         !(((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15))
         hipLaunchKernelGGL(nn_norm_apply4_kernel, dim3(ew_grid(n_out / 4)), dim3(kNnThreads), 0, ctx->stream, x, y, gamma, beta, (const float*)stats,
-                           (unsigned)(n_out / 4), (unsigned)R, C, act);
+                           (const float*)(stats + 2 * G), (unsigned)(n_out / 4), (unsigned)R, C, act);
     else
         hipLaunchKernelGGL(nn_norm_apply_kernel, dim3(ew_grid(n_out)), dim3(kNnThreads), 0, ctx->stream, x, y, gamma, beta,
-                           (const float*)stats, n_out, R, C, act);
+                           (const float*)stats, (const float*)(stats + 2 * G), n_out, R, C, act);
     ALSEP_LAUNCH_CHECK(ctx, "nn_norm_apply_kernel");
     return ALSEP_OK;
 }
