@@ -2800,6 +2800,308 @@ us_pipe_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf16_
     copy_out(nmy - 1);
 }
 
+// ------------------------------------------------------------------------------------------
+// bf16 3x3 convolution, levels 2 and 3 (c = 144 / 192): all output channels against one patch, everything streamed.
+// The plain kernel at c = 192 stages 81 KB per 10.6 MFLOP and re-stages the halo patch for each 48-channel output block;
+// conv3x3_bf16_big_kernel<3> has one patch buffer (its 63 KB DMA is exposed every third stage) and reads 7 fragments per 12 MFMAs.
+// Here, in the structure of conv3x3_bf16_m0_kernel (8 waves, 8 x TW tiles, one pixel row per wave, two patch buffers):
+//  * a wave accumulates ALL Cout = 16 NM channels of its row: NM x TW / 16 accumulator tiles, TW / 16 + NM fragment reads per
+//    NM TW / 16 MFMAs (12 per 27 at c = 144, 15 per 36 at c = 192);
+//  * the weights are a k-step-major image (ConvLayer::w_ac): one k-step of all rows is Cout x 64 B, streamed through a ring of NSLOT
+//    slots of KS k-steps each, DIST = NSLOT - 1 stages ahead.  Each wave copies the same eighth of every slot (whole LDS-DMA
+//    instructions plus one with fewer lanes), so the LDS-DMA count per stage is a constant and nothing is copied twice;
+//  * the patch of the next (tile, chunk) arrives one piece per stage in the other buffer;
+//  * ONE barrier per stage, none per patch.  The barrier of stage s guarantees stage s + 1 (every wave has waited for its pieces of
+//    it), so the fragment reads run one unit (a third or a quarter of a k-step: three 16-row weight blocks) ahead ACROSS the barrier
+//    (within a patch; the first unit of the next patch is requested after a finished tile's stores);
+//  * weight fragments come three at a time in two sets, and there is ONE set of patch fragments: in the last unit of a k-step the
+//    MFMAs run pixel block by pixel block, and a patch fragment that has fed its last MFMA is requested again for the next k-step;
+//    a whole second k-step set would not fit beside 144 accumulators.
+// The k order is the plain kernel's (48-channel chunks, 14 k-steps of groups 4 s + lq, the two padded groups zero): every output
+// element sees the same MFMA sequence -- bit-identical to conv3x3_bf16_kernel.
+// Only ConvAllco<9, 48> (c = 144) is instantiated, tested and measured.  The arithmetic for NM = 12 (UPK = 4) and TW = 64 stays because
+// the c = 192 instance was compiled from it to get its resource report -- 256 VGPRs and 15 more spilled to 64 bytes of scratch per
+// lane -- and is not built for that reason (profiles/conv_allco_ab.txt); nothing launches those instances.
+// ------------------------------------------------------------------------------------------
+template <int NM_, int TW_>
+struct ConvAllco {
+    static constexpr int NM = NM_, TW = TW_, TH = 8, KC = 48, CG = 6, NG = 54, NS = 14, NI = TW / 16, ROWS = 16 * NM, NB = NM, NPAIR = NB / 2;
+    static constexpr int UPK = NM % 4 == 0 ? 4 : 3, G = NM / UPK;   // units per k-step, weight fragments per unit
+    static constexpr int KS = 1, NSLOT = 4, DIST = NSLOT - 1, NSTG = NS / KS, UPS = UPK * KS;  // k-steps per slot, slots, units per stage
+    static constexpr int PW = TW + 2, PH = TH + 2;
+    static constexpr int PGROUPS = PH * PW * CG, PINST = (PGROUPS + 63) / 64, PJ = (PINST + 7) / 8, PBUF = PINST * 64;
+    static constexpr int KSTEP_BYTES = ROWS * 64, SLOT_BYTES = KS * KSTEP_BYTES;
+    static constexpr int WPW = SLOT_BYTES / 8;               // a wave's share of a slot
+    static constexpr int WJ = (WPW + 1023) / 1024, WLAST = (WPW - (WJ - 1) * 1024) / 16;        // its LDS-DMA instructions; lanes of the last
+    static constexpr int ST = NI * (NPAIR + NB % 2);         // epilogue stores per wave and tile
+    static constexpr size_t ring_bytes = 16 * (size_t)(2 * PBUF) + (size_t)NSLOT * SLOT_BYTES;
+    static constexpr size_t lds_bytes = ring_bytes + 2 * ROWS * sizeof(float) + 1024;   // + 1 KiB scratch (surplus patch pieces)
+    static_assert(NM % 3 == 0 && NM % UPK == 0 && TW % 16 == 0 && NS % KS == 0 && SLOT_BYTES % (8 * 16) == 0, "ConvAllco: shape");
+    static_assert(DIST >= 2 && DIST < NSTG && WJ < UPS && PJ - 1 <= NSTG - DIST && NSTG - 1 >= PJ, "ConvAllco: DMA schedule");
+    static_assert(lds_bytes <= 160 * 1024, "ConvAllco: LDS budget");
+    // 64-byte weight rows: lane (l15, lq) reads position lq ^ wswz(row) of row 16 m + l15.  The 16-lane groups of ds_read_b128 hold every
+    // l15 once, {0-3, 12-15} from one lq and {4-11} from its neighbour lq ^ 1: rows l15 & 3 pick the 64-byte quarter of the 256-byte bank
+    // line, and within a quarter the four rows l15 >> 2 = 0, 1, 2, 3 sit at lq, lq ^ 1, lq ^ 1 ^ 2, lq ^ 2 -- four distinct positions.
+    // Enumerated over every row block, slot and lane group: each group touches each of the 64 banks once (profiles/conv_allco_ab.txt).
+    __host__ __device__ static constexpr int wswz(int row) { return ((row >> 3) & 1) << 1; }
+    // Patch fragment of k-step st, lane (l15, lq): group 4 st + lq of the 54 tap-major groups of pixel (wave, l15), i.e. byte
+    // ((wave + tap / 3) PW + tap % 3 + l15) 96 + 16 cg.  Consecutive taps of a patch row are consecutive pixels, so the groups of a
+    // k-step are 16 lq bytes apart from a constant -- xconst(st), an instruction immediate, over the per-lane base
+    // (wave PW + l15) 96 + 16 lq -- except where the k-step crosses from tap 2 to tap 3 (st = 4: the next patch row) and at the two
+    // padded groups (st = 13, lq >= 2: group 53 again, whose weights are zero as in the plain kernel).  Those two k-steps have bases
+    // of their own: three registers instead of NS.
+    __host__ __device__ static constexpr int tapoff(int tap) { return ((tap / 3) * PW + tap % 3) * KC * 2; }
+    __host__ __device__ static constexpr int xconst(int st) { return tapoff(4 * st / CG) + 16 * (4 * st % CG); }
+    __host__ __device__ static constexpr int xkind(int st) { return st == 4 ? 1 : st == NS - 1 ? 2 : 0; }
+    __host__ __device__ static constexpr int xbase(int kind, int wave, int l15, int lq) {
+        const int a = (wave * PW + l15) * KC * 2 + 16 * lq;
+        return kind == 0 ? a : kind == 1 ? a + (lq >= 2 ? (PW - 3) * KC * 2 : 0) : a - (lq >= 2 ? 16 * (lq - 1) : 0);
+    }
+    static_assert(CG == 6 && NS == 14 && NG == 54, "xconst / xkind are written for 54 groups in 14 k-steps");
+    // LDS-DMA instructions of one wave in stage sc of a chunk: its weight pieces, and one patch piece in the first PJ stages
+    __host__ __device__ static constexpr int dma_of_stage(int sc) { return WJ + (sc < PJ ? 1 : 0); }
+    // what may still be in flight at the barrier of stage sc: the DIST - 2 stages before it (stores of a finished tile not counted)
+    __host__ __device__ static constexpr int inflight_at(int sc) {
+        int n = 0;
+        for (int i = 1; i <= DIST - 2; ++i) n += dma_of_stage((sc - i + NSTG) % NSTG);
+        return n;
+    }
+};
+
+// weight fragment reads of unit U = UPK st + t of a chunk: rows 16 (t G + g) + l15 of k-step st
+template <typename Cf, int U>
+__device__ __forceinline__ void allco_read_w(bf16x8 (&wf)[2][Cf::G], const bf16_t* wl) {
+    constexpr int st = U / Cf::UPK, t = U % Cf::UPK;
+    static_for<Cf::G>([&](auto gc) {
+        constexpr int g = decltype(gc)::value;
+        lds_read_async_b128<(t * Cf::G + g) * 1024 + (st % Cf::KS) * Cf::KSTEP_BYTES>(wf[U & 1][g], wl);
+    });
+}
+// patch fragment ni of k-step ST; pb: the patch buffer's LDS address plus the lane's base of that k-step's kind (ConvAllco::xbase)
+template <typename Cf, int ST, int NI>
+__device__ __forceinline__ void allco_read_x(bf16x8& xf, const bf16_t* pb) {
+    lds_read_async_b128<NI * 16 * Cf::KC * 2 + Cf::xconst(ST)>(xf, pb);
+}
+
+template <int NM, int TW>
+__global__ void __launch_bounds__(kBigThreads, 2)
+conv3x3_bf16_allco_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf16_t* __restrict__ Wp, const float* __restrict__ scale,
+                          const float* __restrict__ shift, const bf16_t* __restrict__ zero_page, int Th, int Fw, int Cin, int Cout, int tiles_t,
+                          int tiles_f, int ntiles) {
+    typedef ConvAllco<NM, TW> Cf;
+    bf16_t* const patch0 = reinterpret_cast<bf16_t*>(alsep_smem);
+    bf16_t* const wring = patch0 + (size_t)2 * Cf::PBUF * 8;
+    float* ss = reinterpret_cast<float*>(alsep_smem + Cf::ring_bytes);
+    bf16_t* const scratch = reinterpret_cast<bf16_t*>(alsep_smem + Cf::lds_bytes - 1024);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave: in a scalar register
+    const int l15 = lane & 15, lq = lane >> 4;
+    const int nq = Cin / Cf::KC;
+    for (int i = tid; i < Cf::ROWS; i += kBigThreads) {
+        ss[i] = scale[i];
+        ss[Cf::ROWS + i] = shift[i];
+    }
+    __syncthreads();
+
+    int xb[3];                                               // elements
+#pragma unroll
+    for (int kind = 0; kind < 3; ++kind) xb[kind] = Cf::xbase(kind, wave, l15, lq) / 2;
+    const int wl_off = l15 * 32 + (lq ^ Cf::wswz(l15)) * 8;
+
+    const int my_tiles = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int npatch = my_tiles * nq;
+    auto tile_coords = [&](int k, int& t0, int& f0, int64_t& b) {
+        int tile = (int)blockIdx.x + k * (int)gridDim.x;
+        const int tf = tile % tiles_f;  tile /= tiles_f;
+        const int tt = tile % tiles_t;
+        b = tile / tiles_t;
+        t0 = tt * Cf::TH;
+        f0 = tf * Cf::TW;
+    };
+    // LDS-DMA descriptors of a halo patch, computed once (see conv3x3_bf16_m0_kernel)
+    int prel[Cf::PJ];
+    unsigned pflags[(Cf::PJ + 5) / 6] = {};                  // 5 bits per piece, 6 pieces per word
+#pragma unroll
+    for (int j = 0; j < Cf::PJ; ++j) {
+        const int u = (wave + 8 * j) * 64 + lane;
+        const int uu = u < Cf::PGROUPS ? u : Cf::PGROUPS - 1;
+        const int P = uu / Cf::CG, cg = uu % Cf::CG;
+        const int dt = P / Cf::PW - 1, df = P % Cf::PW - 1;
+        prel[j] = (dt * Fw + df) * Cin + cg * 8;
+        pflags[j / 6] |= (u < Cf::PGROUPS ? (unsigned)((dt < 0) | ((dt >= Cf::TH) << 1) | ((df < 0) << 2) | ((df >= Cf::TW) << 3)) : 16u) << (5 * (j % 6));
+    }
+    // patch ps (tile ps / nq, chunk ps % nq) -> buffer ps & 1; past the last patch the last one is fetched again into the free buffer
+    const bf16_t* psrc = X;
+    unsigned pborder = 0;
+    bf16_t* pdst = patch0;
+    auto patch_prep = [&](int ps) {
+        const int pc = ps < npatch ? ps : npatch - 1;
+        int t0, f0; int64_t b;
+        tile_coords(pc / nq, t0, f0, b);
+        psrc = X + ((b * Th + t0) * (int64_t)Fw + f0) * Cin + (pc % nq) * Cf::KC;
+        pborder = (unsigned)(t0 == 0) | ((unsigned)(t0 + Cf::TH >= Th) << 1) | ((unsigned)(f0 == 0) << 2) | ((unsigned)(f0 + Cf::TW >= Fw) << 3);
+        pdst = patch0 + (size_t)(ps & 1) * Cf::PBUF * 8;
+    };
+    auto patch_one = [&](int j) {
+        const int i = wave + 8 * j;
+        const bool out = (pflags[j / 6] & ((pborder | 16u) << (5 * (j % 6)))) != 0;
+        const bool real = j < Cf::PJ - 1 || i < Cf::PINST;
+        const bf16_t* src = (out || !real) ? zero_page : psrc + opaque_vgpr(prel[j]);      // opaque: sign-extended here, not kept as a pair
+        glds16(src, real ? pdst + (size_t)i * 64 * 8 : scratch);
+    };
+    // weights of stage sc of chunk q -> ring slot: this wave's eighth, WJ instructions (the last one with WLAST lanes)
+    const unsigned wlane = lane * 8;                         // elements
+    const bf16_t* wsrc_next = Wp;                            // wave-uniform: scalar base + 32-bit lane offset
+    bf16_t* wdst_next = wring;
+    auto weights_prep = [&](int q, int sc, int slot) {
+        wsrc_next = Wp + ((size_t)q * Cf::NSTG + sc) * (Cf::SLOT_BYTES / 2) + wave * (Cf::WPW / 2);
+        wdst_next = wring + (size_t)slot * (Cf::SLOT_BYTES / 2) + wave * (Cf::WPW / 2);
+    };
+    auto weights_one = [&](int j) {
+        if (j < Cf::WJ - 1 || Cf::WLAST == 64 || lane < Cf::WLAST) glds16(wsrc_next + (wlane + j * 512u), wdst_next + j * 512);
+    };
+
+    f32x4 acc[Cf::NB][Cf::NI];
+    bf16x8 xf[Cf::NI], wf[2][Cf::G];
+    // the reads of a k-step's first unit, always requested in this order: its weight fragments, then the patch fragments
+    auto read_first = [&](const bf16_t* patch, const bf16_t* wl) {
+        allco_read_w<Cf, 0>(wf, wl);
+        static_for<Cf::NI>([&](auto nic) { allco_read_x<Cf, 0, decltype(nic)::value>(xf[decltype(nic)::value], patch + xb[0]); });
+    };
+    if (npatch > 0) {
+        patch_prep(0);
+#pragma unroll
+        for (int j = 0; j < Cf::PJ; ++j) patch_one(j);
+#pragma unroll
+        for (int d = 0; d < Cf::DIST; ++d) {
+            weights_prep(0, d, d);
+#pragma unroll
+            for (int j = 0; j < Cf::WJ; ++j) weights_one(j);
+        }
+        wait_vmcnt<0>();
+        barrier_nodrain();                                   // patch 0 and stages 0 .. DIST - 1 are in LDS for every wave
+        read_first(patch0, wring + wl_off);
+    }
+    // block pairs outermost: a pair's scale / shift quads are read once and are dead before the next pair's (held across the pixel
+    // blocks for all pairs at once they are 8 NB registers that the accumulators leave no room for)
+    auto epilogue = [&](int k) {
+        int t0, f0; int64_t b;
+        tile_coords(k, t0, f0, b);
+        // the lane's coordinates again, opaque: everything the stores derive from them is computed here, not kept across the k-loops
+        const int le = opaque_vgpr(lane), l15 = le & 15, lq = le >> 4;
+        bf16_t* yb = Y + ((b * Th + t0 + wave) * (int64_t)Fw + f0 + l15) * Cout;
+#pragma unroll
+        for (int j = 0; j < Cf::NPAIR; ++j) {                // blocks 2 j, 2 j + 1: channels 32 j + 8 lq + [0, 8) (ConvBig::channel_of_row)
+            const int co = j * 32 + lq * 8;
+            f32x4 scv[2], shv[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                scv[h] = *reinterpret_cast<const f32x4*>(ss + co + 4 * h);
+                shv[h] = *reinterpret_cast<const f32x4*>(ss + Cf::ROWS + co + 4 * h);
+            }
+#pragma unroll
+            for (int ni = 0; ni < Cf::NI; ++ni) {
+                float y[8];
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) y[4 * h + r] = fmaxf(fmaf(acc[2 * j + h][ni][r], scv[h][r], shv[h][r]), 0.f);
+                store8(yb + (int64_t)ni * 16 * Cout + co, y);
+            }
+        }
+        if constexpr (Cf::NB % 2 == 1) {
+            constexpr int bb = Cf::NB - 1;
+            const int co = bb * 16 + lq * 4;
+            const f32x4 scv = *reinterpret_cast<const f32x4*>(ss + co);
+            const f32x4 shv = *reinterpret_cast<const f32x4*>(ss + Cf::ROWS + co);
+#pragma unroll
+            for (int ni = 0; ni < Cf::NI; ++ni) {
+                float y[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) y[r] = fmaxf(fmaf(acc[bb][ni][r], scv[r], shv[r]), 0.f);
+                store4(yb + (int64_t)ni * 16 * Cout + co, y);
+            }
+        }
+    };
+
+    // Stage (p, sc): k-steps KS sc .. of patch p (tile p / nq, chunk q = p % nq); its weights sit in slot (p NSTG + sc) % NSLOT.
+    // Issued in it, in this order: the weights of stage + DIST (into the slot that the stage before this one has just left), one piece
+    // of patch p + 1, and after the last stage of a tile that tile's stores.  vmcnt counts in order, so the wait at the barrier of a
+    // stage allows exactly what the DIST - 2 stages before it issued (Cf::inflight_at) and, behind those, a finished tile's stores.
+    int slot = 0, q = 0, k = 0;                              // ring slot of the current stage, chunk and tile of the current patch
+    for (int p = 0; p < npatch; ++p) {
+        const bf16_t* const patch = patch0 + (size_t)(p & 1) * Cf::PBUF * 8;
+        const bf16_t* const patch_nx = patch0 + (size_t)((p + 1) & 1) * Cf::PBUF * 8;
+        const int qn = q + 1 == nq ? 0 : q + 1;
+        static_for<Cf::NSTG>([&](auto scc) {
+            constexpr int sc = decltype(scc)::value;
+            if (sc < Cf::DIST - 1 && q == 0 && p > 0) wait_vmcnt<Cf::inflight_at(sc) + Cf::ST>();    // a tile ended inside the window
+            else wait_vmcnt<Cf::inflight_at(sc)>();
+            // raw barrier, no lgkmcnt(0) in front of it: the only LDS reads in flight are those of the next unit, from a slot and a patch
+            // buffer that no wave writes before the barrier after this one
+            __builtin_amdgcn_s_barrier();
+            const int slot_prev = slot == 0 ? Cf::NSLOT - 1 : slot - 1, slot_nx = slot + 1 == Cf::NSLOT ? 0 : slot + 1;
+            weights_prep((sc + Cf::DIST) / Cf::NSTG ? qn : q, (sc + Cf::DIST) % Cf::NSTG, slot_prev);
+            if (sc == 0) {
+                patch_prep(p + 1);
+                if (q == 0) {
+#pragma unroll
+                    for (int b = 0; b < Cf::NB; ++b)
+#pragma unroll
+                        for (int ni = 0; ni < Cf::NI; ++ni) acc[b][ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+                }
+            }
+            const bf16_t* const wl = wring + (size_t)slot * (Cf::SLOT_BYTES / 2) + wl_off;
+            const bf16_t* const wl_nx = wring + (size_t)slot_nx * (Cf::SLOT_BYTES / 2) + wl_off;
+            static_for<Cf::UPS>([&](auto uic) {
+                constexpr int ui = decltype(uic)::value, U = sc * Cf::UPS + ui, t = U % Cf::UPK, st = U / Cf::UPK;
+                constexpr bool chunk_end = U + 1 == Cf::UPK * Cf::NS;
+                constexpr int U1 = chunk_end ? 0 : U + 1, st1 = U1 / Cf::UPK;     // the chunk's last unit requests nothing: see below
+                // in flight, in order: this unit's weight fragments and, with t = 0, the patch fragments behind them
+                if constexpr (t == 0) lds_wait_n<Cf::NI - 1>();
+                else lds_wait_n<0>();
+                if constexpr (!chunk_end) allco_read_w<Cf, U1>(wf, ui + 1 < Cf::UPS ? wl : wl_nx);
+                if constexpr (t == 0) {
+                    // pixel blocks outermost: block ni may still be on its way behind ni - 1
+                    static_for<Cf::NI>([&](auto nic) {
+                        constexpr int ni = decltype(nic)::value;
+                        if constexpr (ni > 0) lds_wait_n<Cf::G + Cf::NI - 1 - ni>();
+#pragma unroll
+                        for (int g = 0; g < Cf::G; ++g) mma_step(acc[t * Cf::G + g][ni], wf[U & 1][g], xf[ni]);
+                    });
+                } else if constexpr (t == Cf::UPK - 1 && !chunk_end) {
+                    // the k-step's last unit, pixel blocks outermost: a patch fragment that has fed its last MFMA is requested again
+                    // for the next k-step into the same registers (one set of patch fragments, not two)
+                    const bf16_t* const pb = patch + xb[Cf::xkind(st1)];
+                    static_for<Cf::NI>([&](auto nic) {
+                        constexpr int ni = decltype(nic)::value;
+#pragma unroll
+                        for (int g = 0; g < Cf::G; ++g) mma_step(acc[t * Cf::G + g][ni], wf[U & 1][g], xf[ni]);
+                        sched_fence();
+                        allco_read_x<Cf, st1, ni>(xf[ni], pb);
+                    });
+                } else {
+#pragma unroll
+                    for (int g = 0; g < Cf::G; ++g)
+#pragma unroll
+                        for (int ni = 0; ni < Cf::NI; ++ni) mma_step(acc[t * Cf::G + g][ni], wf[U & 1][g], xf[ni]);
+                }
+                if constexpr (ui < Cf::WJ) weights_one(ui);
+                if constexpr (ui == Cf::WJ && sc < Cf::PJ) patch_one(sc);
+                sched_fence();
+            });
+            slot = slot_nx;
+            if (sc == Cf::NSTG - 1 && q == nq - 1) epilogue(k);
+        });
+        // the first fragments of the next patch, behind the epilogue: 24 registers that the stores' arithmetic needs (after the last
+        // patch they are read from the refetched copy and never used)
+        read_first(patch_nx, wring + (size_t)slot * (Cf::SLOT_BYTES / 2) + wl_off);
+        q = qn;
+        if (q == 0) ++k;
+    }
+    lds_wait_n<0>();
+    wait_vmcnt<0>();                                         // the surplus LDS-DMA of the last stages lands before the wave ends
+}
+
 #ifndef ALSEP_F16_TU
 #include "tdfnet_f32s.h"     // float32 storage with split-half contractions (the float32 network lives in the main translation unit)
 #endif
@@ -2816,6 +3118,7 @@ struct ConvLayer {       // 3x3
     DevBuf w, scale, shift;
     DevBuf w_big;            // rows in ConvBig::channel_of_row order: conv3x3_bf16_m0_kernel's image (c = 48), conv3x3_bf16_big_kernel<3>'s (c = 144)
     DevBuf w_mq;             // conv3x3_bf16_mq_kernel's image (c = 96)
+    DevBuf w_ac;             // conv3x3_bf16_allco_kernel's k-step-major image (c = 144)
     int cin = 0, cout = 0;
     bool dma_path = false;   // packed for conv3x3_bf16_kernel (swizzled, unpadded)
     int split = 0;           // float32 storage, split-half contraction (tdfnet_f32s.h): 24 = <24, 48> tiles, 16 = <16, 16>
@@ -2963,6 +3266,30 @@ std::vector<bf16_t> pack_conv3x3_mq(const std::vector<float>& w, int cin) {
     return out;
 }
 
+// image of conv3x3_bf16_allco_kernel (c_out = 16 NM): [q][k-step st][16 NM rows][4 groups][8]; row R holds output channel
+// ConvBig<NM / 3>::channel_of_row(R), its group 4 st + lq (tap-major in the 48-channel chunk q, groups 54 and 55 zero) sits at
+// position lq ^ wswz(R)
+template <int NM>
+std::vector<bf16_t> pack_conv3x3_allco(const std::vector<float>& w, int cin) {
+    typedef ConvAllco<NM, 48> Cf;                           // the image does not depend on TW
+    const int nq = cin / Cf::KC;
+    std::vector<bf16_t> out((size_t)nq * Cf::NS * Cf::ROWS * 32, host_cast<bf16_t>(0.f));
+    for (int q = 0; q < nq; ++q)
+        for (int st = 0; st < Cf::NS; ++st)
+            for (int R = 0; R < Cf::ROWS; ++R)
+                for (int lq = 0; lq < 4; ++lq) {
+                    const int grp = 4 * st + lq;
+                    if (grp >= Cf::NG) continue;
+                    const int tap = grp / Cf::CG, cg = grp % Cf::CG, co = ConvBig<NM / 3>::channel_of_row(R);
+                    const size_t dst = ((((size_t)q * Cf::NS + st) * Cf::ROWS + R) * 4 + (lq ^ Cf::wswz(R))) * 8;
+                    for (int e = 0; e < 8; ++e) {
+                        const int ci = q * Cf::KC + cg * 8 + e;
+                        out[dst + e] = host_cast<bf16_t>(w[(((size_t)co * cin + ci) * 3 + tap / 3) * 3 + tap % 3]);
+                    }
+                }
+    return out;
+}
+
 template <typename T> constexpr bool is_bf16() { return false; }
 template <> constexpr bool is_bf16<bf16_t>() { return true; }
 
@@ -2998,6 +3325,10 @@ int make_conv(alsep_net* net, const TensorMap& tm, const std::string& p, int c, 
         if (!rc && c == 144) {                               // level 2: the big-tile kernel
             auto pb = pack_conv3x3_big<3>(*w, c);
             rc = upload(net, pb.data(), pb.size() * sizeof(bf16_t), &L->w_big);
+        }
+        if (!rc && c == 144) {                               // level 2 again: the all-channels kernel
+            auto pa = pack_conv3x3_allco<9>(*w, c);
+            rc = upload(net, pa.data(), pa.size() * sizeof(bf16_t), &L->w_ac);
         }
     } else if (conv_uses_main<T>(c, c)) {
         auto pk = pack_conv3x3<T, ConvSel<T>::KC, ConvSel<T>::BN>(*w, c, c);
@@ -3270,12 +3601,13 @@ int launch_conv_regw(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t
 // image; the caller has checked that the layer fits the kernel.
 template <typename Cf, typename Kern>
 int launch_conv_persist(alsep_ctx* ctx, Kern kern, const ConvLayer& L, const DevBuf& wimg, int prof_class, const char* name, const bf16_t* X,
-                        bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
+                        bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw, int grid_cap = 0) {
     const int tiles_t = Th / Cf::TH, tiles_f = Fw / Cf::TW;
     const int64_t ntiles = B * tiles_t * tiles_f;
     if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
     ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-    const int gx = ntiles < 256 ? (int)ntiles : 256;
+    int gx = ntiles < 256 ? (int)ntiles : 256;
+    if (grid_cap > 0 && gx > grid_cap) gx = grid_cap;
     ProfScope prof(ctx, prof_class);
     prof.work(18.0 * (double)L.cin * L.cout * B * Th * Fw, (double)sizeof(*X) * B * Th * Fw * (L.cin + L.cout));
     hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y, (const bf16_t*)wimg.p,
@@ -3305,6 +3637,26 @@ int launch_conv_m0(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* 
                                        B, Th, Fw);
 }
 
+int conv_allco_grid() {
+    static const int v = env_int("ALSEP_CONV_ALLCO_GRID", 0);
+    return v;
+}
+
+// The pinned launch names count layer launches, whichever instance serves them (as launch_tdf_persist does): the names of the kernel
+// that this one replaces at its level are noted beside its own.
+template <int NM>
+int launch_conv_allco(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
+    typedef ConvAllco<NM, 48> Cf;
+    if (!L.w_ac.p || L.cout != Cf::ROWS || L.cin != L.cout) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no all-channels weight image for this layer");
+    static_assert(NM == 9, "only the c = 144 instance is shipped: the profiling class and the names below are level 2's");
+    if (int rc = launch_conv_persist<Cf>(ctx, conv3x3_bf16_allco_kernel<NM, 48>, L, L.w_ac, ALSEP_PROF_CONV3X3_BIG3, "conv3x3_bf16_allco_kernel", X, Y,
+                                         zero_page, B, Th, Fw, conv_allco_grid()))
+        return rc;
+    note_launch(ctx, "conv3x3_bf16_big_kernel");
+    note_launch(ctx, "conv3x3_bf16_big_kernel<3>");
+    return ALSEP_OK;
+}
+
 // Which kernel runs a bf16 / f16 3x3 conv with c % 48 == 0.  Every switch is an environment variable read once per process; each one only
 // chooses between kernels that compute the same layer (all but mq bit-identically to the plain kernel).
 //   ALSEP_CONV_M0     1 (default): c = 48 with T % 8 == 0, F % 48 == 0 and >= 256 tiles on conv3x3_bf16_m0_kernel (LDS-resident weights);
@@ -3318,10 +3670,20 @@ int launch_conv_m0(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* 
 //                     bench shape (profiles/r02_conv_level1_ab.txt): big-tile 316 us -> merged 262 us -> this 210-219 us per launch
 //                     (1.13 PFLOP/s = 45 % of 2.5 PF).
 //   ALSEP_CONV_BIG3   1 (default): c = 144 on conv3x3_bf16_big_kernel<3> (8 VGPRs spill, outside the MFMA loops); 0: the plain kernel.
+//   ALSEP_CONV_ALLCO  under ALSEP_CONV_BIG and ALSEP_CONV_BIG3 (either at 0 keeps meaning "plain kernel"): c = 144 with T % 8 == 0 and
+//                     F % 48 == 0 on conv3x3_bf16_allco_kernel<9, 48> (all output channels per patch, k-step-major weight ring, two patch
+//                     buffers).  1 (default): the levels in kConvAllcoRouted, at exactly the shapes big<3> would take (F % 64 == 0 as
+//                     well, >= 96 tiles of 8 x 64 or ALSEP_CONV_BIG=2) -- the kernel was measured against big<3> only, so a shape with
+//                     F % 48 == 0 but F % 64 != 0 stays on the plain kernel; 0: never; 2: every shape the kernel serves, without the
+//                     minimum tile count (tests).  ALSEP_CONV_ALLCO_GRID=n caps its grid (tests).  Same-box traces at the bench shape
+//                     (profiles/conv_allco_kernel_stats.txt): big<3> 1051 us (min 1002) -> 773 us (max 828) per launch = 1.23 PFLOP/s =
+//                     0.49 of 2.5 PF.  Its launches also count under big<3>'s pinned names (layer launches, whichever instance serves them).
 //   ALSEP_CONV_NYFAST 1 (default): the plain kernel's Cout / 48 workgroups of one tile run back to back on one XCD (1-D grid, needs
 //                     ntiles % 8 == 0); 0: the tile index is the fastest grid dimension.
-// Everything else -- c = 192 and up (NY = 4 spills heavily at 2 waves / SIMD with ROCm 7.2), shapes that miss a divisibility above -- runs
-// conv3x3_bf16_kernel<64 | 32 | 16>.
+// Everything else -- c = 192 and up, shapes that miss a divisibility above -- runs conv3x3_bf16_kernel<64 | 32 | 16>.  At c = 192 both
+// 8-wave structures need scratch at 2 waves / SIMD with ROCm 7.2 and are not built: big<4> spills heavily, and
+// conv3x3_bf16_allco_kernel<12, 48> (144 accumulators) needs 256 VGPRs and spills 15 more (64 bytes of scratch per lane, hipcc
+// -Rpass-analysis=kernel-resource-usage; profiles/conv_allco_ab.txt).
 int conv_m0_enabled() {
     static const int v = env_int("ALSEP_CONV_M0", 1);
     return v;
@@ -3343,6 +3705,15 @@ int conv_big3_enabled() {
     return v;
 }
 
+int conv_allco_enabled() {
+    static const int v = env_int("ALSEP_CONV_ALLCO", 1);
+    return v;
+}
+// Levels that measured faster on conv3x3_bf16_allco_kernel than on their kernel, same box, bench shape (profiles/conv_allco_kernel_stats.txt,
+// conv_allco_ab.txt); only these are routed there by default.
+constexpr int kConvAllco144 = 1;
+constexpr int kConvAllcoRouted = kConvAllco144;
+
 int run_conv_dma(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zp, int64_t B, int Th, int Fw) {
     if (conv_m0_enabled() && L.cin == 48 && L.cout == 48 && Th % 8 == 0 && Fw % 48 == 0 &&
         (conv_m0_enabled() >= 2 || B * (Th / 8) * (Fw / 48) >= 256))
@@ -3351,6 +3722,12 @@ int run_conv_dma(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y,
         if (L.cin == 48 && conv_regw_enabled() == 3) return launch_conv_regw<1>(ctx, L, X, Y, zp, B, Th, Fw);
         if (L.cin == 48) return launch_conv_regw<1, 3, 2, 32>(ctx, L, X, Y, zp, B, Th, Fw);
         if (L.cin == 96 && conv_regw_enabled() >= 2) return launch_conv_regw<2>(ctx, L, X, Y, zp, B, Th, Fw);
+    }
+    if (conv_big_enabled() && conv_big3_enabled() && conv_allco_enabled() && Th % 8 == 0 && Fw % 48 == 0 && L.cin == 144 && L.cout == 144) {
+        const int mode = conv_allco_enabled();
+        // by default only what big<3> served (F % 64 == 0 too, its tile floor): the shapes the routing was measured at
+        const bool big3_shape = Fw % 64 == 0 && (conv_big_enabled() >= 2 || B * (Th / 8) * (Fw / 64) >= 96);
+        if (mode >= 2 || ((kConvAllcoRouted & kConvAllco144) && big3_shape)) return launch_conv_allco<9>(ctx, L, X, Y, zp, B, Th, Fw);
     }
     if (conv_big_enabled() && Th % 8 == 0 && Fw % 64 == 0 && L.cin == L.cout &&
         (conv_big_enabled() >= 2 || B * (Th / 8) * (Fw / 64) >= 96)) {
