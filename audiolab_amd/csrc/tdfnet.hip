@@ -2819,12 +2819,19 @@ us_pipe_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf16_
 //    a whole second k-step set would not fit beside 144 accumulators.
 // The k order is the plain kernel's (48-channel chunks, 14 k-steps of groups 4 s + lq, the two padded groups zero): every output
 // element sees the same MFMA sequence -- bit-identical to conv3x3_bf16_kernel.
-// Only ConvAllco<9, 48> (c = 144) is instantiated, tested and measured.  The arithmetic for NM = 12 (UPK = 4) and TW = 64 stays because
-// the c = 192 instance was compiled from it to get its resource report -- 256 VGPRs and 15 more spilled to 64 bytes of scratch per
-// lane -- and is not built for that reason (profiles/conv_allco_ab.txt); nothing launches those instances.
+// Output groups (NGRP > 1): a layer of Cout = NGRP x 16 NM channels runs on the instance of 16 NM rows.  A work item is (tile, group); a
+// workgroup takes the NGRP groups of one tile back to back -- item it is tile blockIdx.x + (it / NGRP) gridDim.x, group it % NGRP -- so
+// the patch pieces of a tile's later groups come from the cache that its first group filled.  The weight image is one group image after
+// another (pack_conv3x3_allco of each 16 NM-row slice), scale / shift of all Cout rows sit in LDS, and the epilogue adds the group's
+// channel offset; the rings, the counted waits, the barrier per stage and the read-ahead run over items as they run over tiles, so
+// every output element still sees the plain kernel's MFMA sequence.  The price: the patch is staged once per group, not once per tile.
+// Instances: <9, 48> in one group (c = 144, level 2), <6, 48> and <6, 64> in two groups (c = 192, level 3) and in three (c = 288,
+// tests only).  One group of 12 row blocks at c = 192 -- conv3x3_bf16_allco_kernel<12, 48>, 144 accumulators -- needs 256 VGPRs and
+// spills 15 more to scratch and is not built (profiles/conv_allco_ab.txt); the arithmetic for UPK = 4 stays from that compile.
 // ------------------------------------------------------------------------------------------
-template <int NM_, int TW_>
+template <int NM_, int TW_, int NGRP_ = 1>
 struct ConvAllco {
+    static constexpr int NGRP = NGRP_, COUT = NGRP_ * 16 * NM_;       // output groups of 16 NM rows each; the layer's channels
     static constexpr int NM = NM_, TW = TW_, TH = 8, KC = 48, CG = 6, NG = 54, NS = 14, NI = TW / 16, ROWS = 16 * NM, NB = NM, NPAIR = NB / 2;
     static constexpr int UPK = NM % 4 == 0 ? 4 : 3, G = NM / UPK;   // units per k-step, weight fragments per unit
     static constexpr int KS = 1, NSLOT = 4, DIST = NSLOT - 1, NSTG = NS / KS, UPS = UPK * KS;  // k-steps per slot, slots, units per stage
@@ -2835,8 +2842,8 @@ struct ConvAllco {
     static constexpr int WJ = (WPW + 1023) / 1024, WLAST = (WPW - (WJ - 1) * 1024) / 16;        // its LDS-DMA instructions; lanes of the last
     static constexpr int ST = NI * (NPAIR + NB % 2);         // epilogue stores per wave and tile
     static constexpr size_t ring_bytes = 16 * (size_t)(2 * PBUF) + (size_t)NSLOT * SLOT_BYTES;
-    static constexpr size_t lds_bytes = ring_bytes + 2 * ROWS * sizeof(float) + 1024;   // + 1 KiB scratch (surplus patch pieces)
-    static_assert(NM % 3 == 0 && NM % UPK == 0 && TW % 16 == 0 && NS % KS == 0 && SLOT_BYTES % (8 * 16) == 0, "ConvAllco: shape");
+    static constexpr size_t lds_bytes = ring_bytes + 2 * COUT * sizeof(float) + 1024;   // + 1 KiB scratch (surplus patch pieces)
+    static_assert(NGRP >= 1 && NM % 3 == 0 && NM % UPK == 0 && TW % 16 == 0 && NS % KS == 0 && SLOT_BYTES % (8 * 16) == 0, "ConvAllco: shape");
     static_assert(DIST >= 2 && DIST < NSTG && WJ < UPS && PJ - 1 <= NSTG - DIST && NSTG - 1 >= PJ, "ConvAllco: DMA schedule");
     static_assert(lds_bytes <= 160 * 1024, "ConvAllco: LDS budget");
     // 64-byte weight rows: lane (l15, lq) reads position lq ^ wswz(row) of row 16 m + l15.  The 16-lane groups of ds_read_b128 hold every
@@ -2883,12 +2890,12 @@ __device__ __forceinline__ void allco_read_x(bf16x8& xf, const bf16_t* pb) {
     lds_read_async_b128<NI * 16 * Cf::KC * 2 + Cf::xconst(ST)>(xf, pb);
 }
 
-template <int NM, int TW>
+template <int NM, int TW, int NGRP>
 __global__ void __launch_bounds__(kBigThreads, 2)
 conv3x3_bf16_allco_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf16_t* __restrict__ Wp, const float* __restrict__ scale,
                           const float* __restrict__ shift, const bf16_t* __restrict__ zero_page, int Th, int Fw, int Cin, int Cout, int tiles_t,
                           int tiles_f, int ntiles) {
-    typedef ConvAllco<NM, TW> Cf;
+    typedef ConvAllco<NM, TW, NGRP> Cf;
     bf16_t* const patch0 = reinterpret_cast<bf16_t*>(alsep_smem);
     bf16_t* const wring = patch0 + (size_t)2 * Cf::PBUF * 8;
     float* ss = reinterpret_cast<float*>(alsep_smem + Cf::ring_bytes);
@@ -2896,9 +2903,9 @@ conv3x3_bf16_allco_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // wave: in a scalar register
     const int l15 = lane & 15, lq = lane >> 4;
     const int nq = Cin / Cf::KC;
-    for (int i = tid; i < Cf::ROWS; i += kBigThreads) {
+    for (int i = tid; i < Cf::COUT; i += kBigThreads) {
         ss[i] = scale[i];
-        ss[Cf::ROWS + i] = shift[i];
+        ss[Cf::COUT + i] = shift[i];
     }
     __syncthreads();
 
@@ -2908,7 +2915,7 @@ conv3x3_bf16_allco_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, 
     const int wl_off = l15 * 32 + (lq ^ Cf::wswz(l15)) * 8;
 
     const int my_tiles = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int npatch = my_tiles * nq;
+    const int npatch = my_tiles * Cf::NGRP * nq;             // a patch per (item, chunk); item it = (tile it / NGRP, group it % NGRP)
     auto tile_coords = [&](int k, int& t0, int& f0, int64_t& b) {
         int tile = (int)blockIdx.x + k * (int)gridDim.x;
         const int tf = tile % tiles_f;  tile /= tiles_f;
@@ -2929,14 +2936,14 @@ conv3x3_bf16_allco_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, 
         prel[j] = (dt * Fw + df) * Cin + cg * 8;
         pflags[j / 6] |= (u < Cf::PGROUPS ? (unsigned)((dt < 0) | ((dt >= Cf::TH) << 1) | ((df < 0) << 2) | ((df >= Cf::TW) << 3)) : 16u) << (5 * (j % 6));
     }
-    // patch ps (tile ps / nq, chunk ps % nq) -> buffer ps & 1; past the last patch the last one is fetched again into the free buffer
+    // patch ps (item ps / nq, chunk ps % nq) -> buffer ps & 1; past the last patch the last one is fetched again into the free buffer
     const bf16_t* psrc = X;
     unsigned pborder = 0;
     bf16_t* pdst = patch0;
     auto patch_prep = [&](int ps) {
         const int pc = ps < npatch ? ps : npatch - 1;
         int t0, f0; int64_t b;
-        tile_coords(pc / nq, t0, f0, b);
+        tile_coords(pc / nq / Cf::NGRP, t0, f0, b);
         psrc = X + ((b * Th + t0) * (int64_t)Fw + f0) * Cin + (pc % nq) * Cf::KC;
         pborder = (unsigned)(t0 == 0) | ((unsigned)(t0 + Cf::TH >= Th) << 1) | ((unsigned)(f0 == 0) << 2) | ((unsigned)(f0 + Cf::TW >= Fw) << 3);
         pdst = patch0 + (size_t)(ps & 1) * Cf::PBUF * 8;
@@ -2948,12 +2955,13 @@ conv3x3_bf16_allco_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, 
         const bf16_t* src = (out || !real) ? zero_page : psrc + opaque_vgpr(prel[j]);      // opaque: sign-extended here, not kept as a pair
         glds16(src, real ? pdst + (size_t)i * 64 * 8 : scratch);
     };
-    // weights of stage sc of chunk q -> ring slot: this wave's eighth, WJ instructions (the last one with WLAST lanes)
+    // weights of stage sc of chunk q of group g -> ring slot: this wave's eighth, WJ instructions (the last one with WLAST lanes)
     const unsigned wlane = lane * 8;                         // elements
     const bf16_t* wsrc_next = Wp;                            // wave-uniform: scalar base + 32-bit lane offset
     bf16_t* wdst_next = wring;
-    auto weights_prep = [&](int q, int sc, int slot) {
-        wsrc_next = Wp + ((size_t)q * Cf::NSTG + sc) * (Cf::SLOT_BYTES / 2) + wave * (Cf::WPW / 2);
+    auto weights_prep = [&](int g, int q, int sc, int slot) {
+        const int gq = Cf::NGRP > 1 ? g * nq + q : q;        // group images one after another, nq chunks each
+        wsrc_next = Wp + ((size_t)gq * Cf::NSTG + sc) * (Cf::SLOT_BYTES / 2) + wave * (Cf::WPW / 2);
         wdst_next = wring + (size_t)slot * (Cf::SLOT_BYTES / 2) + wave * (Cf::WPW / 2);
     };
     auto weights_one = [&](int j) {
@@ -2973,7 +2981,7 @@ conv3x3_bf16_allco_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, 
         for (int j = 0; j < Cf::PJ; ++j) patch_one(j);
 #pragma unroll
         for (int d = 0; d < Cf::DIST; ++d) {
-            weights_prep(0, d, d);
+            weights_prep(0, 0, d, d);
 #pragma unroll
             for (int j = 0; j < Cf::WJ; ++j) weights_one(j);
         }
@@ -2983,20 +2991,22 @@ conv3x3_bf16_allco_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, 
     }
     // block pairs outermost: a pair's scale / shift quads are read once and are dead before the next pair's (held across the pixel
     // blocks for all pairs at once they are 8 NB registers that the accumulators leave no room for)
-    auto epilogue = [&](int k) {
+    auto epilogue = [&](int k, int g) {
         int t0, f0; int64_t b;
         tile_coords(k, t0, f0, b);
         // the lane's coordinates again, opaque: everything the stores derive from them is computed here, not kept across the k-loops
         const int le = opaque_vgpr(lane), l15 = le & 15, lq = le >> 4;
-        bf16_t* yb = Y + ((b * Th + t0 + wave) * (int64_t)Fw + f0 + l15) * Cout;
+        const int c0 = Cf::NGRP > 1 ? g * Cf::ROWS : 0;      // the group's first channel
+        bf16_t* yb = Y + ((b * Th + t0 + wave) * (int64_t)Fw + f0 + l15) * Cout + c0;
+        const float* const ssg = ss + c0;                    // the group's scale rows; its shift rows are COUT further on
 #pragma unroll
         for (int j = 0; j < Cf::NPAIR; ++j) {                // blocks 2 j, 2 j + 1: channels 32 j + 8 lq + [0, 8) (ConvBig::channel_of_row)
             const int co = j * 32 + lq * 8;
             f32x4 scv[2], shv[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                scv[h] = *reinterpret_cast<const f32x4*>(ss + co + 4 * h);
-                shv[h] = *reinterpret_cast<const f32x4*>(ss + Cf::ROWS + co + 4 * h);
+                scv[h] = *reinterpret_cast<const f32x4*>(ssg + co + 4 * h);
+                shv[h] = *reinterpret_cast<const f32x4*>(ssg + Cf::COUT + co + 4 * h);
             }
 #pragma unroll
             for (int ni = 0; ni < Cf::NI; ++ni) {
@@ -3011,8 +3021,8 @@ conv3x3_bf16_allco_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, 
         if constexpr (Cf::NB % 2 == 1) {
             constexpr int bb = Cf::NB - 1;
             const int co = bb * 16 + lq * 4;
-            const f32x4 scv = *reinterpret_cast<const f32x4*>(ss + co);
-            const f32x4 shv = *reinterpret_cast<const f32x4*>(ss + Cf::ROWS + co);
+            const f32x4 scv = *reinterpret_cast<const f32x4*>(ssg + co);
+            const f32x4 shv = *reinterpret_cast<const f32x4*>(ssg + Cf::COUT + co);
 #pragma unroll
             for (int ni = 0; ni < Cf::NI; ++ni) {
                 float y[4];
@@ -3023,24 +3033,26 @@ conv3x3_bf16_allco_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, 
         }
     };
 
-    // Stage (p, sc): k-steps KS sc .. of patch p (tile p / nq, chunk q = p % nq); its weights sit in slot (p NSTG + sc) % NSLOT.
-    // Issued in it, in this order: the weights of stage + DIST (into the slot that the stage before this one has just left), one piece
-    // of patch p + 1, and after the last stage of a tile that tile's stores.  vmcnt counts in order, so the wait at the barrier of a
-    // stage allows exactly what the DIST - 2 stages before it issued (Cf::inflight_at) and, behind those, a finished tile's stores.
-    int slot = 0, q = 0, k = 0;                              // ring slot of the current stage, chunk and tile of the current patch
+    // Stage (p, sc): k-steps KS sc .. of patch p (item p / nq = (tile k, group g), chunk q = p % nq); its weights sit in slot
+    // (p NSTG + sc) % NSLOT.  Issued in it, in this order: the weights of stage + DIST (into the slot that the stage before this one has
+    // just left), one piece of patch p + 1, and after the last stage of an item that item's stores.  vmcnt counts in order, so the wait
+    // at the barrier of a stage allows exactly what the DIST - 2 stages before it issued (Cf::inflight_at) and, behind those, a finished
+    // item's stores.
+    int slot = 0, q = 0, k = 0, g = 0;                       // ring slot of the current stage; chunk, tile and group of the current patch
     for (int p = 0; p < npatch; ++p) {
         const bf16_t* const patch = patch0 + (size_t)(p & 1) * Cf::PBUF * 8;
         const bf16_t* const patch_nx = patch0 + (size_t)((p + 1) & 1) * Cf::PBUF * 8;
         const int qn = q + 1 == nq ? 0 : q + 1;
+        const int gn = Cf::NGRP > 1 && qn == 0 ? (g + 1 == Cf::NGRP ? 0 : g + 1) : g;      // the group of patch p + 1
         static_for<Cf::NSTG>([&](auto scc) {
             constexpr int sc = decltype(scc)::value;
-            if (sc < Cf::DIST - 1 && q == 0 && p > 0) wait_vmcnt<Cf::inflight_at(sc) + Cf::ST>();    // a tile ended inside the window
+            if (sc < Cf::DIST - 1 && q == 0 && p > 0) wait_vmcnt<Cf::inflight_at(sc) + Cf::ST>();    // an item ended inside the window
             else wait_vmcnt<Cf::inflight_at(sc)>();
             // raw barrier, no lgkmcnt(0) in front of it: the only LDS reads in flight are those of the next unit, from a slot and a patch
             // buffer that no wave writes before the barrier after this one
             __builtin_amdgcn_s_barrier();
             const int slot_prev = slot == 0 ? Cf::NSLOT - 1 : slot - 1, slot_nx = slot + 1 == Cf::NSLOT ? 0 : slot + 1;
-            weights_prep((sc + Cf::DIST) / Cf::NSTG ? qn : q, (sc + Cf::DIST) % Cf::NSTG, slot_prev);
+            weights_prep((sc + Cf::DIST) / Cf::NSTG ? gn : g, (sc + Cf::DIST) / Cf::NSTG ? qn : q, (sc + Cf::DIST) % Cf::NSTG, slot_prev);
             if (sc == 0) {
                 patch_prep(p + 1);
                 if (q == 0) {
@@ -3090,13 +3102,14 @@ conv3x3_bf16_allco_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, 
                 sched_fence();
             });
             slot = slot_nx;
-            if (sc == Cf::NSTG - 1 && q == nq - 1) epilogue(k);
+            if (sc == Cf::NSTG - 1 && q == nq - 1) epilogue(k, g);
         });
         // the first fragments of the next patch, behind the epilogue: 24 registers that the stores' arithmetic needs (after the last
         // patch they are read from the refetched copy and never used)
         read_first(patch_nx, wring + (size_t)slot * (Cf::SLOT_BYTES / 2) + wl_off);
         q = qn;
-        if (q == 0) ++k;
+        g = gn;
+        if (q == 0 && g == 0) ++k;                           // the tile's last group is done
     }
     lds_wait_n<0>();
     wait_vmcnt<0>();                                         // the surplus LDS-DMA of the last stages lands before the wave ends
@@ -3118,7 +3131,7 @@ struct ConvLayer {       // 3x3
     DevBuf w, scale, shift;
     DevBuf w_big;            // rows in ConvBig::channel_of_row order: conv3x3_bf16_m0_kernel's image (c = 48), conv3x3_bf16_big_kernel<3>'s (c = 144)
     DevBuf w_mq;             // conv3x3_bf16_mq_kernel's image (c = 96)
-    DevBuf w_ac;             // conv3x3_bf16_allco_kernel's k-step-major image (c = 144)
+    DevBuf w_ac;             // conv3x3_bf16_allco_kernel's k-step-major image (c = 144; c = 192 / 288: one image per group of 96 rows)
     int cin = 0, cout = 0;
     bool dma_path = false;   // packed for conv3x3_bf16_kernel (swizzled, unpadded)
     int split = 0;           // float32 storage, split-half contraction (tdfnet_f32s.h): 24 = <24, 48> tiles, 16 = <16, 16>
@@ -3328,6 +3341,15 @@ int make_conv(alsep_net* net, const TensorMap& tm, const std::string& p, int c, 
         }
         if (!rc && c == 144) {                               // level 2 again: the all-channels kernel
             auto pa = pack_conv3x3_allco<9>(*w, c);
+            rc = upload(net, pa.data(), pa.size() * sizeof(bf16_t), &L->w_ac);
+        }
+        if (!rc && (c == 192 || c == 288)) {                 // the all-channels kernel in output groups of 96 rows: one image per group
+            std::vector<bf16_t> pa;
+            const size_t slice = (size_t)96 * c * 9;
+            for (int g = 0; g < c / 96; ++g) {
+                auto pg = pack_conv3x3_allco<6>(std::vector<float>(w->begin() + g * slice, w->begin() + (g + 1) * slice), c);
+                pa.insert(pa.end(), pg.begin(), pg.end());
+            }
             rc = upload(net, pa.data(), pa.size() * sizeof(bf16_t), &L->w_ac);
         }
     } else if (conv_uses_main<T>(c, c)) {
@@ -3644,16 +3666,27 @@ int conv_allco_grid() {
 
 // The pinned launch names count layer launches, whichever instance serves them (as launch_tdf_persist does): the names of the kernel
 // that this one replaces at its level are noted beside its own.
-template <int NM>
+// <9, 48, 1> replaces conv3x3_bf16_big_kernel<3> (c = 144); the instances in output groups, <6, 48 | 64, 2 | 3> (c = 192 / 288), replace
+// conv3x3_bf16_kernel<64 | small> and keep its profiling class, so that a level's class does not depend on the instance that serves it.
+template <int NM, int TW, int NGRP>
 int launch_conv_allco(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
-    typedef ConvAllco<NM, 48> Cf;
-    if (!L.w_ac.p || L.cout != Cf::ROWS || L.cin != L.cout) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no all-channels weight image for this layer");
-    static_assert(NM == 9, "only the c = 144 instance is shipped: the profiling class and the names below are level 2's");
-    if (int rc = launch_conv_persist<Cf>(ctx, conv3x3_bf16_allco_kernel<NM, 48>, L, L.w_ac, ALSEP_PROF_CONV3X3_BIG3, "conv3x3_bf16_allco_kernel", X, Y,
+    typedef ConvAllco<NM, TW, NGRP> Cf;
+    static_assert((NM == 9 && TW == 48 && NGRP == 1) || (NM == 6 && NGRP >= 2), "an instance that has a weight image, names and a class below");
+    if (!L.w_ac.p || L.cout != Cf::COUT || L.cin != L.cout || Th % Cf::TH || Fw % TW)
+        return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no all-channels weight image for this layer, or not its shape");
+    const bool plain64 = Fw >= 64 && Fw % 64 == 0;           // run_conv_dma's choice between conv3x3_bf16_kernel<64> and <small>
+    const int prof_class = NGRP == 1 ? ALSEP_PROF_CONV3X3_BIG3 : plain64 ? ALSEP_PROF_CONV3X3 : ALSEP_PROF_CONV3X3_SMALL;
+    if (int rc = launch_conv_persist<Cf>(ctx, conv3x3_bf16_allco_kernel<NM, TW, NGRP>, L, L.w_ac, prof_class, "conv3x3_bf16_allco_kernel", X, Y,
                                          zero_page, B, Th, Fw, conv_allco_grid()))
         return rc;
-    note_launch(ctx, "conv3x3_bf16_big_kernel");
-    note_launch(ctx, "conv3x3_bf16_big_kernel<3>");
+    if (NGRP == 1) {
+        note_launch(ctx, "conv3x3_bf16_big_kernel");
+        note_launch(ctx, "conv3x3_bf16_big_kernel<3>");
+    } else {
+        note_launch(ctx, TW == 48 ? "conv3x3_bf16_allco_kernel<6,48>" : "conv3x3_bf16_allco_kernel<6,64>");
+        note_launch(ctx, "conv3x3_bf16_kernel");
+        note_launch(ctx, plain64 ? "conv3x3_bf16_kernel<64>" : "conv3x3_bf16_kernel<small>");
+    }
     return ALSEP_OK;
 }
 
@@ -3678,12 +3711,23 @@ int launch_conv_allco(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_
 //                     minimum tile count (tests).  ALSEP_CONV_ALLCO_GRID=n caps its grid (tests).  Same-box traces at the bench shape
 //                     (profiles/conv_allco_kernel_stats.txt): big<3> 1051 us (min 1002) -> 773 us (max 828) per launch = 1.23 PFLOP/s =
 //                     0.49 of 2.5 PF.  Its launches also count under big<3>'s pinned names (layer launches, whichever instance serves them).
+//                     Under ALSEP_CONV_BIG alone: c = 192 / 288 with T % 8 == 0 and F % TW == 0 on conv3x3_bf16_allco_kernel<6, TW, 2 | 3>,
+//                     the same kernel in two / three output groups of 96 channels (a work item is (tile, group); the patch is staged once
+//                     per group).  1 (default): c = 192 if kConvAllcoRouted has its bit, at the shapes it was measured against
+//                     conv3x3_bf16_kernel<64> (F % 64 == 0 as well, >= 96 tiles of 8 x 64 or ALSEP_CONV_BIG=2); c = 288 never (level 5 is
+//                     0.24 ms per forward: nothing to gain); 0: never; 2: every shape an instance serves, c = 288 too, without the minimum
+//                     tile count (tests).  These launches keep the plain kernel's profiling class and also count under its pinned names,
+//                     and under conv3x3_bf16_allco_kernel<6,48> or <6,64>.  Same-box traces at the bench shape
+//                     (profiles/conv_allco_groups_kernel_stats.txt): conv3x3_bf16_kernel<64> 523 us (min 493) -> <6, 64, 2> 346 us
+//                     (max 381) per launch = 1.23 PFLOP/s = 0.49 of 2.5 PF; <6, 48, 2> 377 us (max 410) = 0.45.
+//   ALSEP_CONV_ALLCO_TW  48 | 64 (default 64, the width that measured faster): the tile width of the instances in output groups (tests, A/B).
 //   ALSEP_CONV_NYFAST 1 (default): the plain kernel's Cout / 48 workgroups of one tile run back to back on one XCD (1-D grid, needs
 //                     ntiles % 8 == 0); 0: the tile index is the fastest grid dimension.
-// Everything else -- c = 192 and up, shapes that miss a divisibility above -- runs conv3x3_bf16_kernel<64 | 32 | 16>.  At c = 192 both
-// 8-wave structures need scratch at 2 waves / SIMD with ROCm 7.2 and are not built: big<4> spills heavily, and
-// conv3x3_bf16_allco_kernel<12, 48> (144 accumulators) needs 256 VGPRs and spills 15 more (64 bytes of scratch per lane, hipcc
-// -Rpass-analysis=kernel-resource-usage; profiles/conv_allco_ab.txt).
+// Everything else -- c = 240 and up, shapes that miss a divisibility above -- runs conv3x3_bf16_kernel<64 | 32 | 16>.  At c = 192 both
+// 8-wave structures need scratch at 2 waves / SIMD with ROCm 7.2 when one wave holds all 192 channels, and are not built that way:
+// big<4> spills heavily, and conv3x3_bf16_allco_kernel<12, 48> (144 accumulators) needs 256 VGPRs and spills 15 more (64 bytes of
+// scratch per lane, hipcc -Rpass-analysis=kernel-resource-usage; profiles/conv_allco_ab.txt).  In two groups of 96 channels the
+// all-channels kernel holds 72 (8 x 48) or 96 (8 x 64) accumulators: 158 / 201 VGPRs, no scratch (profiles/conv_allco_groups_ab.txt).
 int conv_m0_enabled() {
     static const int v = env_int("ALSEP_CONV_M0", 1);
     return v;
@@ -3710,9 +3754,15 @@ int conv_allco_enabled() {
     return v;
 }
 // Levels that measured faster on conv3x3_bf16_allco_kernel than on their kernel, same box, bench shape (profiles/conv_allco_kernel_stats.txt,
-// conv_allco_ab.txt); only these are routed there by default.
-constexpr int kConvAllco144 = 1;
-constexpr int kConvAllcoRouted = kConvAllco144;
+// conv_allco_ab.txt; c = 192: conv_allco_groups_kernel_stats.txt, conv_allco_groups_ab.txt); only these are routed there by default.
+constexpr int kConvAllco144 = 1, kConvAllco192 = 2;
+constexpr int kConvAllcoRouted = kConvAllco144 | kConvAllco192;
+// the tile width of the instances in output groups (c = 192 / 288): 48 or 64
+constexpr int kConvAllcoTw = 64;
+int conv_allco_tw() {
+    static const int v = env_int("ALSEP_CONV_ALLCO_TW", kConvAllcoTw) == 48 ? 48 : 64;
+    return v;
+}
 
 int run_conv_dma(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zp, int64_t B, int Th, int Fw) {
     if (conv_m0_enabled() && L.cin == 48 && L.cout == 48 && Th % 8 == 0 && Fw % 48 == 0 &&
@@ -3727,7 +3777,16 @@ int run_conv_dma(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y,
         const int mode = conv_allco_enabled();
         // by default only what big<3> served (F % 64 == 0 too, its tile floor): the shapes the routing was measured at
         const bool big3_shape = Fw % 64 == 0 && (conv_big_enabled() >= 2 || B * (Th / 8) * (Fw / 64) >= 96);
-        if (mode >= 2 || ((kConvAllcoRouted & kConvAllco144) && big3_shape)) return launch_conv_allco<9>(ctx, L, X, Y, zp, B, Th, Fw);
+        if (mode >= 2 || ((kConvAllcoRouted & kConvAllco144) && big3_shape)) return launch_conv_allco<9, 48, 1>(ctx, L, X, Y, zp, B, Th, Fw);
+    }
+    if (conv_big_enabled() && conv_allco_enabled() && L.cin == L.cout && (L.cout == 192 || L.cout == 288)) {
+        const int mode = conv_allco_enabled(), tw = conv_allco_tw();
+        // by default only c = 192, and only where conv3x3_bf16_kernel<64> ran it with the tile floor of the other 8-wave kernels
+        const bool measured_shape = L.cout == 192 && Fw % 64 == 0 && (conv_big_enabled() >= 2 || B * (Th / 8) * (Fw / 64) >= 96);
+        if (Th % 8 == 0 && Fw % tw == 0 && (mode >= 2 || ((kConvAllcoRouted & kConvAllco192) && measured_shape))) {
+            if (L.cout == 192) return tw == 48 ? launch_conv_allco<6, 48, 2>(ctx, L, X, Y, zp, B, Th, Fw) : launch_conv_allco<6, 64, 2>(ctx, L, X, Y, zp, B, Th, Fw);
+            return tw == 48 ? launch_conv_allco<6, 48, 3>(ctx, L, X, Y, zp, B, Th, Fw) : launch_conv_allco<6, 64, 3>(ctx, L, X, Y, zp, B, Th, Fw);
+        }
     }
     if (conv_big_enabled() && Th % 8 == 0 && Fw % 64 == 0 && L.cin == L.cout &&
         (conv_big_enabled() >= 2 || B * (Th / 8) * (Fw / 64) >= 96)) {
