@@ -239,6 +239,15 @@ _SIGNATURES = {
     "alsep_master_limit_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "alsep_master_pcm24": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_void_p, C.c_int64, C.c_void_p]),
+    "alsep_tempo_frames": (C.c_int64, [C.c_int64]),
+    "alsep_tempo_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "alsep_tempo_flux_workspace_bytes": (C.c_int64, []),
+    "alsep_tempo_flux": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "alsep_tempo_env_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "alsep_tempo_tempogram_workspace_bytes": (C.c_int64, []),
+    "alsep_tempo_tempogram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "alsep_tempo_local_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "alsep_tempo_beat_dp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "alsep_mix_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(MixStem), C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
                                 C.c_void_p]),
     "alsep_mix_power_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),

@@ -758,3 +758,4 @@ extern "C" int alsep_reverb_envelope_db(alsep_ctx* ctx, const float* x, int c, i
 #include "pitch.h"
 #include "compare.h"
 #include "master.h"
+#include "tempo.h"

@@ -617,6 +617,33 @@ int alsep_master_limit_apply(alsep_ctx* ctx, const double* lr, int64_t n, int64_
  * even, clipped to +/-8388607, little-endian 3-byte samples, L R interleaved */
 int alsep_master_pcm24(alsep_ctx* ctx, const double* lr, int64_t n, int64_t ld, double divisor, double* result, int64_t ld_res, uint8_t* pcm);
 
+/* ---- tempo and beat tracking: replaces librosa.load + librosa.beat.beat_track of wrappers/export.py:18-40 (csrc/tempo.h; parity unpinned,
+ * specification tests/tempo_oracle.py).  Fixed geometry: 22050 Hz, n_fft 2048, hop 512, centred frames (F = 1 + n / 512), 128 mel bands,
+ * tempogram window 344.  Float64 throughout; every pointer is a device pointer unless it says otherwise. */
+/* F for n samples; -1 when n < 1 or n is more than 60 minutes */
+int64_t alsep_tempo_frames(int64_t n);
+/* mel [128][F] = filterbank . |rfft(frame window)|^2.  window: periodic Hann [2048]; twiddle: exp(-2 pi i m / 2048) as (re, im) pairs [2048];
+ * bands: int32 [128][3] = first bin, bin count, offset into weights [n_weights] */
+int alsep_tempo_mel(alsep_ctx* ctx, const double* y, int64_t n, const double* window, const double* twiddle, const int32_t* bands,
+                    const double* weights, int64_t n_weights, double* mel);
+/* db [128][frames] = max(D, max(D) - 80), D = 10 log10(max(1e-10, mel)); env [frames]: 3 zeros, then the median over the bands of
+ * max(0, db[:, t] - db[:, t - 1]) for t = 1 .., cut to `frames` values */
+int64_t alsep_tempo_flux_workspace_bytes(void);
+int alsep_tempo_flux(alsep_ctx* ctx, const double* mel, int64_t frames, double* db, double* env, void* ws, int64_t ws_bytes);
+/* stats [3] = max|env|, mean(env), std(env, ddof = 1) */
+int alsep_tempo_env_stats(alsep_ctx* ctx, const double* env, int64_t frames, double* stats);
+/* tg [344] = the mean over the frames of autocorrelate(window . frame) / max|.|, the frames 344 long, hop 1, over env padded by 172 with a
+ * linear ramp to 0 on both sides.  window: periodic Hann [344] */
+int64_t alsep_tempo_tempogram_workspace_bytes(void);
+int alsep_tempo_tempogram(alsep_ctx* ctx, const double* env, int64_t frames, const double* window, double* tg, void* ws, int64_t ws_bytes);
+/* ls = scipy.signal.convolve(env / stats[2], window, "same"); window [2 period + 1], 1 <= period <= 343 */
+int alsep_tempo_local_score(alsep_ctx* ctx, const double* env, int64_t frames, const double* stats, const double* window, int period, double* ls);
+/* Ellis' beat recursion over the offsets first_offset .. first_offset + count - 1 (all negative, at most 576 of them, first_offset >= -686):
+ * cand[j] = txwt[j] + cum[i + offset j] (0 before the start); b = the lowest index among the maxima; cum[i] = ls[i] + cand[b];
+ * back[i] (int32) = -1 until a frame has ls[i] >= 0.01 max(ls), i + offset b from then on.  Additions and comparisons only. */
+int alsep_tempo_beat_dp(alsep_ctx* ctx, const double* ls, int64_t frames, const double* txwt, int first_offset, int count, double* cum,
+                        int32_t* back);
+
 /* ---- stem mixdown with loudness matching: replaces the pydub calls of wrappers/merge.py:15-45,146-151 (AudioSegment.overlay,
  * effects.normalize, .dBFS, .apply_gain), i.e. audioop.add / max / rms / mul, on the signed integer grid of `bits` (16 or 32) with
  * full scale M = 2^(bits-1).  The mix is int32 [channels][n] (row stride ld) for both widths; channels * n <= 2^31.
