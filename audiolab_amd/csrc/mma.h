@@ -11,6 +11,18 @@
 #pragma once
 #include "alsep_common.h"
 
+#include <utility>
+
+template <typename F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+// f(std::integral_constant<int, 0>) ... f(std::integral_constant<int, N - 1>): loop indices that instruction immediates need
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+    static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
 template <typename T> struct Frag;
 template <> struct Frag<bf16_t> {
     typedef bf16x8 type;
