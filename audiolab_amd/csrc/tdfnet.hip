@@ -2153,8 +2153,247 @@ us_pipe_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf16_
     copy_out(nmy - 1);
 }
 
+// ------------------------------------------------------------------------------------------
+// Both TDF linears of a block in one launch (levels 2 and 3: F = 768 / 384, hidden H = F / 8, C a multiple of 48):
+//   y = x + relu(bn2(W2 . relu(bn1(W1 . x + b1)) + b2))
+// with the arithmetic of the two tdf_bf16_kernel launches it replaces -- x fragments are the MFMA A operand by transpose read, a
+// 32-wide k-step is composed as there, k ascends within every accumulator, the hidden tile is rounded to the storage type, bias,
+// BN, ReLU and the residual add are fp32 with one rounding -- so the output is the same bits.  Different traffic: x is read from
+// memory once, y is written once, the hidden tensor never leaves the CU.
+//   * a work item is 768 tile rows of 48 channels: one unit (one (b, t), one 48-channel group) at F = 768, two consecutive units at
+//     F = 384; persistent 8-wave workgroups, one per CU, stride statically over the items;
+//   * the item's tile (72 KiB) comes into one of two LDS buffers by LDS-DMA, nine 1 KiB pieces per wave, requested behind the
+//     first barrier of the item before -- it lands under that item's MFMAs and stores; it is the A operand of the first linear and
+//     the residual of the second;
+//   * ALL weight fragments stay in registers for the whole launch, loaded once per wave from fragment-order images
+//     (make_tdf_fused_weights): waves 0..5 own one 16-row m-tile of the hidden tile each (F / 32 fragments: 96 VGPRs at F = 768), every
+//     wave owns tile rows [96 w, 96 w + 96) of the second linear (6 m-tiles x ceil(H / 32) fragments: 72 VGPRs).  Inside the item
+//     loop a wave issues nothing that counts on vmcnt but its nine LDS-DMAs and, behind them, its nine stores, so the one wait per
+//     item is vmcnt(9): the tile has landed, the stores of the item before may still be in flight;
+//   * phase A: waves 0..5, 3 accumulators over F / 32 k-steps, fragment reads one k-step ahead; relu(bn1(.)) rounded into the hidden
+//     tile [H (+ zero rows up to a multiple of 32)][48] in LDS.  Barrier.  Phase B: per 16-row m-tile 3 accumulators over the hidden
+//     tile's k-steps (the all-zero k-step that Kp = 128 adds at H = 96 is left out: it adds +0 to accumulators that are never -0);
+//     the lane reads its residual values from the tile, adds, rounds once and writes the result over them; then the wave's 96 rows
+//     leave as nine whole-row 16-byte stores per lane;
+//   * two barriers per item (tile landed / hidden tile complete); every LDS access in the item loop is asm with its own lgkmcnt
+//     wait (a compiler-tracked one would be given s_waitcnt vmcnt(0) for the LDS-DMA in flight, as in ds_pipe_kernel).
+// LDS: 2 x 72 KiB + 9 / 12 KiB hidden + 3 KiB scale / shift = 156 / 159 KiB.
+// ------------------------------------------------------------------------------------------
+template <int F_>
+struct TdfFused {
+    static constexpr int F = F_, H = F_ / 8, UC = 48, WV = 8, THREADS = 64 * WV;
+    static constexpr int ROWS = 768, NU = ROWS / F_;                 // tile rows of an item; units per item
+    static constexpr int KS1 = F_ / 32, HM = H / 16;                 // k-steps of the first linear; m-tiles of a unit's hidden tile
+    static constexpr int HR = (H + 31) / 32 * 32, KS2 = HR / 32;     // hidden rows per unit in LDS (zero beyond H); k-steps of the second
+    static constexpr int WR = ROWS / WV, MT2 = WR / 16;              // tile rows and m-tiles of a wave in phase B
+    static constexpr int ND = WR * UC * (int)sizeof(bf16_t) / 1024;  // LDS-DMA pieces, and stores, per wave and item: 9
+    static constexpr int WA = NU * HM;                               // waves of phase A
+    static constexpr int CMAX = 192;                                 // channels the scale / shift table holds
+    static constexpr size_t tile_bytes = (size_t)ROWS * UC * sizeof(bf16_t);
+    static constexpr size_t h_bytes = (size_t)NU * HR * UC * sizeof(bf16_t);
+    static constexpr size_t lds_bytes = 2 * tile_bytes + h_bytes + 4 * CMAX * sizeof(float);
+    static_assert(NU * F_ == ROWS && H % 16 == 0 && WA <= WV && F_ % WR == 0 && ND * 1024 == WR * UC * (int)sizeof(bf16_t) && WR % 32 == 0,
+                  "fused TDF geometry");
+    static_assert(lds_bytes <= 160 * 1024, "LDS of a CU");
+};
+
+#ifdef ALSEP_CPU_EMUL
+template <int OFF>
+static inline void lds_read_async_b64(bf16x4& dst, const bf16_t* lds_ptr) { std::memcpy(&dst, reinterpret_cast<const char*>(lds_ptr) + OFF, 8); }
+#else
+// lds_read_async_b128 for four 16-bit values
+template <int OFF>
+__device__ __forceinline__ void lds_read_async_b64(bf16x4& dst, const bf16_t* lds_ptr) {
+    static_assert(OFF >= 0 && OFF < 65536 && OFF % 8 == 0, "ds offset field");
+    const unsigned addr = (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void*)lds_ptr;
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
+}
+#endif
+
+template <int F_>
+__global__ void __launch_bounds__(TdfFused<F_>::THREADS, 1)
+tdf_bf16_fused_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf16_t* __restrict__ W1f,
+                      const bf16_t* __restrict__ W2f, const float* __restrict__ bias1, const float* __restrict__ scale1,
+                      const float* __restrict__ shift1, const float* __restrict__ bias2, const float* __restrict__ scale2,
+                      const float* __restrict__ shift2, int nitems, int C) {
+    typedef TdfFused<F_> P;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, lq = lane >> 4;
+    char* tiles = alsep_smem;
+    bf16_t* ht = reinterpret_cast<bf16_t*>(alsep_smem + 2 * P::tile_bytes);
+    float* bnl = reinterpret_cast<float*>(alsep_smem + 2 * P::tile_bytes + P::h_bytes);      // [scale1 | shift1 | scale2 | shift2][CMAX]
+    const int upc = C / P::UC;
+
+    for (int i = tid; i < 4 * C; i += P::THREADS) {
+        const int w = i / C, c = i % C;
+        bnl[w * P::CMAX + c] = (w == 0 ? scale1 : (w == 1 ? shift1 : (w == 2 ? scale2 : shift2)))[c];
+    }
+    if (P::HR > P::H) {                                              // the k rows beyond H of the second linear's last k-step
+        constexpr int ZG = (P::HR - P::H) * P::UC / 8;
+        for (int i = tid; i < P::NU * ZG; i += P::THREADS)
+            *reinterpret_cast<bf16x8*>(ht + ((i / ZG) * P::HR + P::H) * P::UC + (i % ZG) * 8) = bf16x8{};
+    }
+
+    // phase A: wave w < WA owns m-tile mia of unit ua's hidden tile; phase B: every wave owns tile rows [WR w, WR w + WR) = rows
+    // [f0, f0 + WR) of unit ub -- the same rows it fills and stores
+    const bool wa = wave < P::WA;
+    const int ua = wa ? wave / P::HM : 0, mia = wa ? wave % P::HM : 0;
+    const int ub = (wave * P::WR) / P::F, f0 = (wave * P::WR) % P::F;
+    bf16x8 w1[P::KS1], w2[P::MT2][P::KS2];
+#pragma unroll
+    for (int ks = 0; ks < P::KS1; ++ks)
+        w1[ks] = wa ? *reinterpret_cast<const bf16x8*>(W1f + ((size_t)(mia * P::KS1 + ks) * 64 + lane) * 8) : bf16x8{};
+    float b2[P::MT2];
+#pragma unroll
+    for (int mi = 0; mi < P::MT2; ++mi) {
+#pragma unroll
+        for (int ks = 0; ks < P::KS2; ++ks)
+            w2[mi][ks] = *reinterpret_cast<const bf16x8*>(W2f + ((size_t)((f0 / 16 + mi) * P::KS2 + ks) * 64 + lane) * 8);
+        b2[mi] = bias2 ? bias2[f0 + mi * 16 + l15] : 0.f;
+    }
+    const float b1 = (wa && bias1) ? bias1[mia * 16 + l15] : 0.f;
+
+    // three pieces of 1 KiB are 32 rows of 96 bytes: piece q of a wave's nine lies (q / 3) * 32 rows below piece q % 3
+    unsigned xoff[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int within = j * 64 + lane;
+        xoff[j] = (unsigned)(((within / 6) * C + (within % 6) * 8) * (int)sizeof(bf16_t));
+    }
+    const int trow = l15 >> 2, tcol = (l15 & 3) * 4;
+    const unsigned xa_off = (unsigned)(((ua * P::F + 4 * lq + trow) * P::UC + tcol) * (int)sizeof(bf16_t));     // phase A fragments, in the tile
+    const bf16_t* hl = ht + (ub * P::HR + 4 * lq + trow) * P::UC + tcol;                                       // phase B fragments
+    bf16_t* hw = ht + (ua * P::HR + mia * 16 + l15) * P::UC + 4 * lq;                                          // phase A result
+    const unsigned eb_off = (unsigned)(((wave * P::WR + l15) * P::UC + 4 * lq) * (int)sizeof(bf16_t));        // phase B residual / result
+    const unsigned co_off = (unsigned)(wave * P::ND * 1024 + lane * 16);                                       // copy-out
+
+    const int nmy = (nitems - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
+    // unit u of this workgroup's item i: its first channel, and the element offset in X / Y of its row 0 there
+    auto unit_cb = [&](int i, int u) { return ((((int)blockIdx.x + i * (int)gridDim.x) * P::NU + u) % upc) * P::UC; };
+    auto unit_base = [&](int i, int u) {
+        const int un = ((int)blockIdx.x + i * (int)gridDim.x) * P::NU + u;
+        return ((int64_t)(un / upc) * P::F) * C + (un % upc) * P::UC;
+    };
+    auto issue = [&](int i) {
+        const ALSEP_GLOBAL char* src = opaque_uniform_gptr(reinterpret_cast<const char*>(X + unit_base(i, ub) + (int64_t)f0 * C));
+        char* dst = tiles + (size_t)(i & 1) * P::tile_bytes + (size_t)wave * (P::ND * 1024);
+#pragma unroll
+        for (int q = 0; q < P::ND; ++q) glds16_base(src + (size_t)(q / 3) * 32 * C * sizeof(bf16_t), xoff[q % 3], dst + q * 1024);
+    };
+
+    wait_vmcnt<0>();                                                 // weights and biases are in registers
+    if (nmy > 0) issue(0);
+    for (int i = 0; i < nmy; ++i) {
+        if (i > 0) wait_vmcnt<P::ND>();                              // behind DMA(i) this wave has issued the ND stores of item i - 1, nothing else
+        else wait_vmcnt<0>();
+        barrier_nodrain();        // tile i is in LDS for every wave (first item: the tables too); item i - 1 is computed and copied out of its buffer
+        if (i + 1 < nmy) issue(i + 1);
+        char* tile = tiles + (size_t)(i & 1) * P::tile_bytes;
+
+        if (wa) {
+            const bf16_t* xl = reinterpret_cast<const bf16_t*>(tile + xa_off);
+            const bf16_t* xl2 = xl + 12 * 32 * P::UC;                // k-steps 12 and up: the ds offset field ends at 64 KiB
+            f32x4 acc[3];
+#pragma unroll
+            for (int ni = 0; ni < 3; ++ni) acc[ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+            bf16x8 xf[2][3];
+            static_for<3>([&](auto nic) {
+                constexpr int ni = decltype(nic)::value;
+                xf[0][ni] = tdfw_read_frag<ni * 32>(xl);
+            });
+            static_for<P::KS1>([&](auto ksc) {
+                constexpr int ks = decltype(ksc)::value, b = ks & 1;
+                if constexpr (ks + 1 < P::KS1) {
+                    constexpr int k1 = ks + 1;
+                    const bf16_t* bp = k1 >= 12 ? xl2 : xl;
+                    static_for<3>([&](auto nic) {
+                        constexpr int ni = decltype(nic)::value;
+                        xf[1 - b][ni] = tdfw_read_frag<(k1 % 12) * 32 * P::UC * 2 + ni * 32>(bp);
+                    });
+                    lds_read_tr16_wait_n<6>();                       // step ks has landed, step ks + 1 is in flight
+                } else {
+                    lds_read_tr16_wait_n<0>();
+                }
+#pragma unroll
+                for (int ni = 0; ni < 3; ++ni) mma_step(acc[ni], xf[b][ni], w1[ks]);
+            });
+            // relu(bn1(acc + b1)), rounded as tdf_bf16_kernel<false> stores it
+            const float* bp = bnl + unit_cb(i, ua) + 4 * lq;
+            f32x4 sc[3], sh[3];
+            static_for<3>([&](auto nic) {
+                constexpr int ni = decltype(nic)::value;
+                lds_read_async_f32x4<ni * 64>(sc[ni], bp);
+                lds_read_async_f32x4<P::CMAX * 4 + ni * 64>(sh[ni], bp);
+            });
+            lds_wait_n<0>();
+            static_for<3>([&](auto nic) {
+                constexpr int ni = decltype(nic)::value;
+                bf16x4 q;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) q[r] = (bf16_t)fmaxf(fmaf(acc[ni][r] + b1, sc[ni][r], sh[ni][r]), 0.f);
+                lds_write_async_b64(hw + ni * 16, q);
+            });
+        }
+        barrier_nodrain();                                           // the hidden tile is complete
+
+        {
+            const float* bp = bnl + 2 * P::CMAX + unit_cb(i, ub) + 4 * lq;
+            bf16_t* el = reinterpret_cast<bf16_t*>(tile + eb_off);
+            static_for<P::MT2>([&](auto mic) {
+                constexpr int mi = decltype(mic)::value;
+                bf16x8 hf[P::KS2][3];
+                static_for<P::KS2 * 3>([&](auto jc) {
+                    constexpr int ks = decltype(jc)::value / 3, ni = decltype(jc)::value % 3;
+                    hf[ks][ni] = tdfw_read_frag<ks * 32 * P::UC * 2 + ni * 32>(hl);
+                });
+                f32x4 acc[3];
+#pragma unroll
+                for (int ni = 0; ni < 3; ++ni) acc[ni] = f32x4{0.f, 0.f, 0.f, 0.f};
+                lds_read_tr16_wait_n<0>();
+#pragma unroll
+                for (int ks = 0; ks < P::KS2; ++ks)
+#pragma unroll
+                    for (int ni = 0; ni < 3; ++ni) mma_step(acc[ni], hf[ks][ni], w2[mi][ks]);
+                // fmaxf(fmaf(acc + b2, scale, shift), 0) + x in fp32, one rounding, as tdf_bf16_kernel<true>; over the residual values
+                bf16x4 xr[3];
+                f32x4 sc[3], sh[3];
+                static_for<3>([&](auto nic) {
+                    constexpr int ni = decltype(nic)::value;
+                    lds_read_async_b64<(mi * 16 * P::UC + ni * 16) * 2>(xr[ni], el);
+                    lds_read_async_f32x4<ni * 64>(sc[ni], bp);
+                    lds_read_async_f32x4<P::CMAX * 4 + ni * 64>(sh[ni], bp);
+                });
+                lds_wait_n<0>();
+                static_for<3>([&](auto nic) {
+                    constexpr int ni = decltype(nic)::value;
+                    bf16x4 q;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        q[r] = (bf16_t)(fmaxf(fmaf(acc[ni][r] + b2[mi], sc[ni][r], sh[ni][r]), 0.f) + (float)xr[ni][r]);
+                    lds_write_async_b64(el + mi * 16 * P::UC + ni * 16, q);
+                });
+            });
+            // the wave's rows, complete: whole 96-byte rows in 16-byte pieces (the LDS operations of a wave execute in order)
+            __builtin_amdgcn_wave_barrier();
+            const bf16_t* cl = reinterpret_cast<const bf16_t*>(tile + co_off);
+            bf16x8 q[P::ND];
+            static_for<P::ND>([&](auto tc) {
+                constexpr int t = decltype(tc)::value;
+                lds_read_async_b128<t * 1024>(q[t], cl);
+            });
+            lds_wait_n<0>();
+            ALSEP_GLOBAL char* yb = const_cast<ALSEP_GLOBAL char*>(
+                opaque_uniform_gptr(reinterpret_cast<const char*>(Y + unit_base(i, ub) + (int64_t)f0 * C)));
+#pragma unroll
+            for (int t = 0; t < P::ND; ++t)
+                stream_store(reinterpret_cast<ALSEP_GLOBAL bf16x8*>(yb + (size_t)(t / 3) * 32 * C * sizeof(bf16_t) + xoff[t % 3]), q[t]);
+        }
+    }
+}
+
 #ifndef ALSEP_F16_TU
-#include "tdfnet_f32s.h"     // float32 storage with split-half contractions (the float32 network lives in the main translation unit)
+#include "tdfnet_f32s.h"    // float32 storage with split-half contractions (the float32 network lives in the main translation unit)
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -2184,6 +2423,7 @@ struct GemmLayer {       // ds / us / tdf
     bool dma_path = false;   // packed for tdf_bf16_kernel
     DevBuf wfrag;            // [m-tile][k-step][lane][8] for the streaming ds/us kernels (bf16, levels 0 <-> 1 <-> 2)
     DevBuf wwide;            // fragment-order image for tdf_bf16_wide_kernel (bf16, M % 192 == 0)
+    DevBuf wfused;           // fragment-order image for tdf_bf16_fused_kernel (both linears of a block with F = 768 / 384, H = F / 8)
 };
 struct Block {
     std::vector<ConvLayer> tfc;
@@ -2466,6 +2706,22 @@ int make_tdf_wide_weights(alsep_net* net, const std::vector<float>& wmk, int M, 
     return upload(net, pk.data(), pk.size() * sizeof(bf16_t), &L->wwide);
 }
 
+// fragment-order image for tdf_bf16_fused_kernel: [M/16][ceil(K/32)][lane 64][8]; lane (l15, lq) of (m-tile mt, k-step ks) holds
+// W[16 mt + l15][32 ks + {4lq..4lq+3, 16+4lq..16+4lq+3}], zero beyond K -- the k order of the two images above
+int make_tdf_fused_weights(alsep_net* net, const std::vector<float>& wmk, int M, int K, GemmLayer* L) {
+    const int MT = M / 16, KS = (K + 31) / 32;
+    std::vector<bf16_t> pk((size_t)MT * KS * 512, host_cast<bf16_t>(0.f));
+    for (int mt = 0; mt < MT; ++mt)
+        for (int ks = 0; ks < KS; ++ks)
+            for (int l = 0; l < 64; ++l)
+                for (int e = 0; e < 8; ++e) {
+                    const int lq = l >> 4, m = mt * 16 + (l & 15);
+                    const int k = ks * 32 + (e < 4 ? 4 * lq + e : 16 + 4 * lq + (e - 4));
+                    if (k < K) pk[(((size_t)mt * KS + ks) * 64 + l) * 8 + e] = host_cast<bf16_t>(wmk[(size_t)m * K + k]);
+                }
+    return upload(net, pk.data(), pk.size() * sizeof(bf16_t), &L->wfused);
+}
+
 // fragment-order image of a [M][K] matrix for register-resident A operands: lane l of (m-tile, k-step) holds
 // W[16*mt + (l & 15)][32*ks + 8*(l >> 4) + e], e < 8 (zero beyond M / K)
 int make_frag_weights(alsep_net* net, const std::vector<float>& wmk, int M, int K, DevBuf* out) {
@@ -2504,6 +2760,8 @@ int make_block(alsep_net* net, const TensorMap& tm, const std::string& p, int c,
                                                : make_gemm_weights<T>(net, *w, fo, fi, L);
         if (rc) return rc;
         if (L->dma_path && fo % 192 == 0 && (rc = make_tdf_wide_weights(net, *w, fo, fi, L))) return rc;
+        if (L->dma_path && n_lin == 2 && cfg.bn == 8 && (f == 768 || f == 384) && (rc = make_tdf_fused_weights(net, *w, fo, fi, L)))
+            return rc;
         if ((rc = upload(net, sc->data(), c * sizeof(float), &L->scale))) return rc;
         if ((rc = upload(net, sh->data(), c * sizeof(float), &L->shift))) return rc;
         auto bi = find(tm, q + ".bias", fo, net->ctx, false);
@@ -3224,6 +3482,55 @@ int run_tdf(alsep_ctx* ctx, const GemmLayer& L, const T* X, T* Y, const T* R, in
     return ALSEP_OK;
 }
 
+// ALSEP_TDF_FUSED: 1 (default) = the two TDF linears of a block run as one launch of tdf_bf16_fused_kernel at the levels in
+// kTdfFusedRouted (a level is routed there only where, in kernel traces of one session, the fused launch's mean and max lay below
+// the sum of the two old launches' minima: profiles/tdf_fused_kernel_stats.txt), and only at no fewer items than the level was
+// measured at (kTdfFusedFloor: the bench's 52 windows -- 9984 items at F = 768, 3328 at F = 384; below that the workgroups run
+// fewer rounds and nothing was measured); 0 = never (two launches of tdf_bf16_kernel, as before); 2 = every shape an instance
+// serves (bf16 / f16 on the DMA path, bn = 8, F = 768 or 384, C a multiple of 48 up to 192), without the floor (tests).
+// ALSEP_TDF_FUSED_GRID=n caps its grid (tests: several items per workgroup at small shapes).
+enum { kTdfFusedF768 = 1, kTdfFusedF384 = 2 };
+constexpr int kTdfFusedRouted = kTdfFusedF768 | kTdfFusedF384;
+constexpr int64_t kTdfFusedFloor[2] = {9984, 3328};
+int tdf_fused_mode() {
+    static const int v = env_int("ALSEP_TDF_FUSED", 1);
+    return v;
+}
+template <int F_>
+int launch_tdf_fused(alsep_ctx* ctx, const GemmLayer& A, const GemmLayer& B, const bf16_t* X, bf16_t* Y, int64_t nitems, int C) {
+    typedef TdfFused<F_> P;
+    static const int cap = env_int("ALSEP_TDF_FUSED_GRID", 0);
+    int64_t grid = device_cu_count(ctx);                             // 156 / 159 KiB of LDS: one workgroup per CU
+    if (cap > 0 && cap < grid) grid = cap;
+    if (nitems < grid) grid = nitems;
+    ProfScope prof(ctx, ALSEP_PROF_TDF);
+    ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)tdf_bf16_fused_kernel<F_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P::lds_bytes));
+    hipLaunchKernelGGL((tdf_bf16_fused_kernel<F_>), dim3((unsigned)grid), dim3(P::THREADS), P::lds_bytes, ctx->stream, X, Y,
+                       (const bf16_t*)A.wfused.p, (const bf16_t*)B.wfused.p, A.has_bias ? (const float*)A.bias.p : nullptr,
+                       (const float*)A.scale.p, (const float*)A.shift.p, B.has_bias ? (const float*)B.bias.p : nullptr,
+                       (const float*)B.scale.p, (const float*)B.shift.p, (int)nitems, C);
+    note_launch(ctx, "tdf_bf16_kernel");                             // the pinned name counts layer launches, whichever instance
+    note_launch(ctx, "tdf_bf16_kernel");                             // serves them: this launch is two of them
+    ALSEP_LAUNCH_CHECK(ctx, "tdf_bf16_fused_kernel");
+    return ALSEP_OK;
+}
+// Both linears of blk as one launch where ALSEP_TDF_FUSED routes it (*done); otherwise nothing is launched and the caller runs them.
+int run_tdf_fused(alsep_ctx* ctx, const Block& blk, const bf16_t* X, bf16_t* Y, int64_t BT, int C, bool* done) {
+    const GemmLayer& A = blk.tdf[0];
+    const GemmLayer& B = blk.tdf[1];
+    const int mode = tdf_fused_mode();
+    if (mode <= 0 || !A.dma_path || !B.dma_path || !A.wfused.p || !B.wfused.p || C % 48 != 0 || C > TdfFused<768>::CMAX) return ALSEP_OK;
+    const bool f768 = B.M == 768;
+    const int64_t nunits = BT * (C / 48);
+    const int nu = f768 ? TdfFused<768>::NU : TdfFused<384>::NU;
+    if (nunits <= 0 || nunits % nu != 0 || nunits > 0x7fffffff) return ALSEP_OK;
+    const int64_t nitems = nunits / nu;
+    if (mode == 1 && (!(kTdfFusedRouted & (f768 ? kTdfFusedF768 : kTdfFusedF384)) || nitems < kTdfFusedFloor[f768 ? 0 : 1])) return ALSEP_OK;
+    *done = true;
+    return f768 ? launch_tdf_fused<768>(ctx, A, B, X, Y, nitems, C) : launch_tdf_fused<384>(ctx, A, B, X, Y, nitems, C);
+}
+int run_tdf_fused(alsep_ctx*, const Block&, const float*, float*, int64_t, int, bool*) { return ALSEP_OK; }     // float32: never
+
 // TFC_TDF block: cur -> dest, using scratch a, b (cur may alias b), hidden h.  fin (last block of the network only): the
 // residual TDF launch may produce the network's output instead of dest (FinalFold).
 template <typename T>
@@ -3239,6 +3546,8 @@ int run_block(alsep_ctx* ctx, const alsep_net* net, const Block& blk, const T* c
         src = dst;
     }
     if (blk.tdf.size() == 2) {
+        bool fused = false;
+        if ((rc = run_tdf_fused(ctx, blk, src, dest, B * Th, c, &fused)) || fused) return rc;
         if ((rc = run_tdf<T>(ctx, blk.tdf[0], src, h, (const T*)nullptr, B * Th, c, net->zero_page.p))) return rc;
         return run_tdf<T>(ctx, blk.tdf[1], h, dest, src, B * Th, c, net->zero_page.p, fin);
     }
