@@ -262,6 +262,14 @@ _SIGNATURES = {
     "alsep_nn_blstm_stitch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int] * 5),
     "alsep_nn_group_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
                                       C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "alsep_rmvpe_frames": (C.c_int64, [C.c_int64]),
+    "alsep_rmvpe_mel": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "alsep_rmvpe_pad_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_float]),
+    "alsep_rmvpe_avgpool2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "alsep_rmvpe_tconv3x3s2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_int] * 7),
+    "alsep_nn_gru": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "alsep_rmvpe_sigmoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "alsep_rmvpe_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
 }
 
 EXPORTS: Tuple[str, ...] = tuple(_SIGNATURES)

@@ -1667,3 +1667,4 @@ extern "C" int alsep_vr_band_spec(alsep_ctx* ctx, const float* spec_m, const flo
 }
 
 #include "nn_hdemucs.h"
+#include "rmvpe.h"

@@ -697,6 +697,38 @@ int64_t alsep_mix_ratecv_length(int64_t n, int64_t in_rate, int64_t out_rate);
 int alsep_mix_sum_rates(alsep_ctx* ctx, const alsep_mix_operand* operands, int n_operands, int channels, int64_t n_out, int bits,
                         int32_t* acc, int64_t ld_acc, uint32_t* peak);
 
+/* ---- RMVPE pitch extraction: replaces the RMVPE class of modules/rvc/infer/lib/rmvpe.py (csrc/rmvpe.h).  Float32, the decode in float64;
+ * channels-last tensors; every pointer is a device pointer. ---- */
+/* frames of n samples at 16 kHz: n / 160 + 1; -1 when n < 1 or the count is above 2^20 */
+int64_t alsep_rmvpe_frames(int64_t n);
+/* the log-mel front end (rmvpe.py:475-555, :113-149): the track reflected by 512 samples at both ends (folded as often as a short
+ * track needs), frames of 1024 every 160, window [1024], the float32 magnitude of 513 bins, basis [128][513] . magnitude, and
+ * mel_log [T][128] = log(max(., 1e-5)); mel_lin (may be NULL) [T][128]: the product before the clamp.  twiddle: exp(-2 pi i k / 1024) as
+ * (re, im) pairs, k < 512; bands: int32 [128][2] = first bin and bin count of every row's non-zero stretch of the basis. */
+int alsep_rmvpe_mel(alsep_ctx* ctx, const float* audio, int64_t n, const float* window, const float* twiddle, const float* basis,
+                    const int32_t* bands, float* mel_lin, float* mel_log);
+/* y [Tp][C] = scale * x[r(t)][C] + shift, r(t) = t below T and 2 (T - 1) - t from there on (mel2hidden's reflection of the frame axis,
+ * rmvpe.py:608-622, with the input BatchNorm of the one channel folded in); ALSEP_ERR_ARG when Tp - T > T - 1 */
+int alsep_rmvpe_pad_frames(alsep_ctx* ctx, const float* x, float* y, int64_t T, int64_t Tp, int C, float scale, float shift);
+/* nn.AvgPool2d(2): x [B, H, W, C] -> y [B, H / 2, W / 2, C]; H and W even.  cat (may be NULL): x is also copied into the channel slice
+ * [cat_coff, cat_coff + C) of cat [B, H, W, cat_ctotal] (the skip half of the decoder's torch.cat) */
+int alsep_rmvpe_avgpool2(alsep_ctx* ctx, const float* x, float* y, int64_t B, int H, int W, int C, float* cat, int cat_ctotal, int cat_coff);
+/* y[..., y_coff : y_coff + Cout] of [B, 2H, 2W, y_ctotal] = act(conv_transpose2d(x, w, stride 2, padding 1, output_padding 1) * scale +
+ * shift); x [B, H, W, Cin]; w packed [3][3][Cin][Cout] from the module's [Cin][Cout][3][3]; act 0 or 1 (ReLU); Cout % 4 == 0 */
+int alsep_rmvpe_tconv3x3s2(alsep_ctx* ctx, const float* x, const float* w, const float* scale, const float* shift, float* y, int64_t B, int H,
+                           int W, int Cin, int Cout, int act, int y_ctotal, int y_coff);
+/* One bidirectional GRU layer's recurrence (torch.nn.GRU, gate order r, z, n; n = tanh(pre_n + r (W_hn h + b_hn))), both directions and
+ * all N sequences in ONE launch:
+ *   pre [T, N, 6H] = x W_ih^T + b_ih of the forward (columns 0 .. 3H) and the reverse direction (3H .. 6H);
+ *   whh_t [2, H, 3H] = W_hh^T and bhh [2, 3H] = b_hh of each direction (forward first);  h [T, N, 2H] = h_t, forward direction first.
+ * Zero initial state.  16 <= H <= 512, H % 16 == 0. */
+int alsep_nn_gru(alsep_ctx* ctx, const float* pre, const float* whh_t, const float* bhh, float* h, int T, int N, int H);
+/* x = 1 / (1 + exp(-x)) in place */
+int alsep_rmvpe_sigmoid(alsep_ctx* ctx, float* x, int64_t n);
+/* to_local_average_cents + decode (rmvpe.py:624-628, :669-687): salience [T][360] float32 -> f0 [T] float64; 0 where the frame's largest
+ * salience <= thred (compared in float32) and where f0 comes out as exactly 10 */
+int alsep_rmvpe_decode(alsep_ctx* ctx, const float* salience, int64_t T, float thred, double* f0);
+
 #ifdef __cplusplus
 }
 #endif
