@@ -2841,158 +2841,12 @@ int build_net(alsep_net* net, const TensorMap& tm) {
     return ALSEP_OK;
 }
 
-// ---- launches ------------------------------------------------------------------------------
-// work of a 3x3 convolution for the profile: 2 x 9 flops per input channel, output channel and pixel; every activation read and written once
-void conv_work(ProfScope& prof, const ConvLayer& L, size_t elem_bytes, int64_t B, int Th, int Fw) {
-    prof.work(18.0 * (double)L.cin * L.cout * B * Th * Fw, (double)elem_bytes * B * Th * Fw * (L.cin + L.cout));
-}
-
-template <typename T, int KC, int BN, int TW>
-int launch_conv(alsep_ctx* ctx, const ConvLayer& L, const T* X, T* Y, int64_t B, int Th, int Fw) {
-    typedef ConvCfg<T, KC, BN, TW> Cf;
-    const int tiles_t = (int)ceil_div64(Th, Cf::TH), tiles_f = (int)ceil_div64(Fw, TW);
-    const int64_t ntiles = B * tiles_t * tiles_f;
-    if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
-    ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_kernel<T, KC, BN, TW>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-    ProfScope prof(ctx, TW == 64 ? ALSEP_PROF_CONV3X3 : ALSEP_PROF_CONV3X3_SMALL);
-    conv_work(prof, L, sizeof(*X), B, Th, Fw);
-    hipLaunchKernelGGL((conv3x3_kernel<T, KC, BN, TW>), dim3((unsigned)ntiles, L.cout / BN), dim3(kThreads),
-                       Cf::lds_bytes, ctx->stream, X, Y, (const T*)L.w.p, (const float*)L.scale.p,
-                       (const float*)L.shift.p, Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles);
-    ALSEP_LAUNCH_CHECK(ctx, "conv3x3_kernel");
-    return ALSEP_OK;
-}
-
-template <typename T, int KC, int BN>
-int run_conv_tw(alsep_ctx* ctx, const ConvLayer& L, const T* X, T* Y, int64_t B, int Th, int Fw) {
-    if (Fw >= 64 && Fw % 64 == 0) return launch_conv<T, KC, BN, 64>(ctx, L, X, Y, B, Th, Fw);
-    if (Fw >= 32) return launch_conv<T, KC, BN, 32>(ctx, L, X, Y, B, Th, Fw);
-    return launch_conv<T, KC, BN, 16>(ctx, L, X, Y, B, Th, Fw);
-}
-
-int conv_ny_fastest() {
-    static const int v = env_int("ALSEP_CONV_NYFAST", 1);
-    return v;
-}
-
-template <int TW>
-int launch_conv_dma(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B,
-                    int Th, int Fw) {
-    typedef ConvB16<TW> Cf;
-    const int tiles_t = (int)ceil_div64(Th, Cf::TH), tiles_f = (int)ceil_div64(Fw, TW);
-    const int64_t ntiles = B * tiles_t * tiles_f;
-    if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
-    ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_kernel<TW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)Cf::lds_bytes));
-    ProfScope prof(ctx, TW == 64 ? ALSEP_PROF_CONV3X3 : ALSEP_PROF_CONV3X3_SMALL);
-    conv_work(prof, L, sizeof(*X), B, Th, Fw);
-    const int nyc = L.cout / Cf::BN;
-    const int ny_fastest = conv_ny_fastest() && ntiles % 8 == 0 && nyc > 1 && ntiles * nyc <= 0x7fffffff;
-    hipLaunchKernelGGL((conv3x3_bf16_kernel<TW>), ny_fastest ? dim3((unsigned)(ntiles * nyc)) : dim3((unsigned)ntiles, nyc),
-                       dim3(kThreads), Cf::lds_bytes,
-                       ctx->stream, X, Y, (const bf16_t*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page,
-                       Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles, /*ablate*/ 0, /*stagger*/ 0, ny_fastest);
-    note_launch(ctx, TW == 64 ? "conv3x3_bf16_kernel<64>" : "conv3x3_bf16_kernel<small>");
-    ALSEP_LAUNCH_CHECK(ctx, "conv3x3_bf16_kernel");
-    return ALSEP_OK;
-}
-
-template <int NQ, int RING_ = 3, int OCC = 1, int TW_ = 64>
-int launch_conv_regw(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B,
-                     int Th, int Fw) {
-    typedef ConvRW<NQ, RING_, TW_> Cf;
-    const int tiles_t = Th / Cf::TH, tiles_f = Fw / Cf::TW;
-    const int64_t ntiles = B * tiles_t * tiles_f;
-    if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
-    ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_bf16_regw_kernel<NQ, RING_, OCC, TW_>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-    const int ny = L.cout / Cf::BN;
-    int gx = OCC * 256 / ny;                                // OCC workgroups per CU over the whole grid
-    if (gx > ntiles) gx = (int)ntiles;
-    ProfScope prof(ctx, ALSEP_PROF_CONV3X3_REGW);
-    conv_work(prof, L, sizeof(*X), B, Th, Fw);
-    hipLaunchKernelGGL((conv3x3_bf16_regw_kernel<NQ, RING_, OCC, TW_>), dim3((unsigned)gx, ny), dim3(kThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                       (const bf16_t*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin,
-                       L.cout, tiles_t, tiles_f, (int)ntiles);
-    ALSEP_LAUNCH_CHECK(ctx, "conv3x3_bf16_regw_kernel");
-    return ALSEP_OK;
-}
-
-// The three 8-wave persistent convs (conv3x3_bf16_m0_kernel, _mq_kernel, _big_kernel<3>) share their argument list and their launch: one
-// workgroup per CU, each walking the tiles blockIdx.x, blockIdx.x + gridDim.x, ...  Cf is the kernel's tile configuration, wimg its weight
-// image; the caller has checked that the layer fits the kernel.
-template <typename Cf, typename Kern>
-int launch_conv_persist(alsep_ctx* ctx, Kern kern, const ConvLayer& L, const DevBuf& wimg, int prof_class, const char* name, const bf16_t* X,
-                        bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw, int grid_cap = 0) {
-    const int tiles_t = Th / Cf::TH, tiles_f = Fw / Cf::TW;
-    const int64_t ntiles = B * tiles_t * tiles_f;
-    if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
-    ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::lds_bytes));
-    int gx = ntiles < 256 ? (int)ntiles : 256;
-    if (grid_cap > 0 && gx > grid_cap) gx = grid_cap;
-    ProfScope prof(ctx, prof_class);
-    conv_work(prof, L, sizeof(*X), B, Th, Fw);
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, ctx->stream, X, Y, (const bf16_t*)wimg.p,
-                       (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles);
-    ALSEP_LAUNCH_CHECK(ctx, name);
-    return ALSEP_OK;
-}
-
-int launch_conv_big3(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
-    if (!L.w_big.p) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no big-tile weight image for this layer");
-    if (int rc = launch_conv_persist<ConvBig<3>>(ctx, conv3x3_bf16_big_kernel<3>, L, L.w_big, ALSEP_PROF_CONV3X3_BIG3, "conv3x3_bf16_big_kernel",
-                                                 X, Y, zero_page, B, Th, Fw))
-        return rc;
-    note_launch(ctx, "conv3x3_bf16_big_kernel<3>");
-    return ALSEP_OK;
-}
-
-int launch_conv_mq(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
-    if (!L.w_mq.p || L.cout != ConvMq::ROWS || L.cin % ConvMq::KC) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no mq weight image for this layer");
-    return launch_conv_persist<ConvMq>(ctx, conv3x3_bf16_mq_kernel, L, L.w_mq, ALSEP_PROF_CONV3X3_BIG, "conv3x3_bf16_mq_kernel", X, Y, zero_page,
-                                       B, Th, Fw);
-}
-
-int launch_conv_m0(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
-    if (!L.w_big.p || L.cout != ConvM0::ROWS || L.cin != ConvM0::KC) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no m0 weight image for this layer");
-    return launch_conv_persist<ConvM0>(ctx, conv3x3_bf16_m0_kernel, L, L.w_big, ALSEP_PROF_CONV3X3_REGW, "conv3x3_bf16_m0_kernel", X, Y, zero_page,
-                                       B, Th, Fw);
-}
-
-int conv_allco_grid() {
-    static const int v = env_int("ALSEP_CONV_ALLCO_GRID", 0);
-    return v;
-}
-
-// The pinned launch names count layer launches, whichever instance serves them (as launch_tdf_persist does): the names of the kernel
-// that this one replaces at its level are noted beside its own.
-// <9, 48, 1> replaces conv3x3_bf16_big_kernel<3> (c = 144); the instances in output groups, <6, 48 | 64, 2 | 3> (c = 192 / 288), replace
-// conv3x3_bf16_kernel<64 | small> and keep its profiling class, so that a level's class does not depend on the instance that serves it.
-template <int NM, int TW, int NGRP>
-int launch_conv_allco(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
-    typedef ConvAllco<NM, TW, NGRP> Cf;
-    static_assert((NM == 9 && TW == 48 && NGRP == 1) || (NM == 6 && NGRP >= 2), "an instance that has a weight image, names and a class below");
-    if (!L.w_ac.p || L.cout != Cf::COUT || L.cin != L.cout || Th % Cf::TH || Fw % TW)
-        return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no all-channels weight image for this layer, or not its shape");
-    const bool plain64 = Fw >= 64 && Fw % 64 == 0;           // run_conv_dma's choice between conv3x3_bf16_kernel<64> and <small>
-    const int prof_class = NGRP == 1 ? ALSEP_PROF_CONV3X3_BIG3 : plain64 ? ALSEP_PROF_CONV3X3 : ALSEP_PROF_CONV3X3_SMALL;
-    if (int rc = launch_conv_persist<Cf>(ctx, conv3x3_bf16_allco_kernel<NM, TW, NGRP>, L, L.w_ac, prof_class, "conv3x3_bf16_allco_kernel", X, Y,
-                                         zero_page, B, Th, Fw, conv_allco_grid()))
-        return rc;
-    if (NGRP == 1) {
-        note_launch(ctx, "conv3x3_bf16_big_kernel");
-        note_launch(ctx, "conv3x3_bf16_big_kernel<3>");
-    } else {
-        note_launch(ctx, TW == 48 ? "conv3x3_bf16_allco_kernel<6,48>" : "conv3x3_bf16_allco_kernel<6,64>");
-        note_launch(ctx, "conv3x3_bf16_kernel");
-        note_launch(ctx, plain64 ? "conv3x3_bf16_kernel<64>" : "conv3x3_bf16_kernel<small>");
-    }
-    return ALSEP_OK;
-}
-
-// Which kernel runs a bf16 / f16 3x3 conv with c % 48 == 0.  Every switch is an environment variable read once per process; each one only
-// chooses between kernels that compute the same layer (all but mq bit-identically to the plain kernel).
+// ---- switches ------------------------------------------------------------------------------
+// Which kernel runs a layer of a bf16 / f16 network on the DMA and stream paths.  Every switch is an environment variable (atoi of it, or
+// the default where it is not set), read once per process by switches(); each one only chooses between kernels that compute the same
+// layer (all but mq bit-identically).  The routing itself is route_conv_dma, route_pix_stream, route_tdf_dma and route_tdf_fused below.
+//
+// 3x3 convs with c % 48 == 0
 //   ALSEP_CONV_M0     1 (default): c = 48 with T % 8 == 0, F % 48 == 0 and >= 256 tiles on conv3x3_bf16_m0_kernel (LDS-resident weights);
 //                     2: without the minimum tile count (tests); 0: off.  Same-box A/B at the bench shape (profiles/r02_conv_level0_ab.txt):
 //                     register-weight kernel 268.5 us -> 233 us per 1.12 GB launch (4.8 TB/s = 60 % of 8 TB/s).
@@ -3029,77 +2883,291 @@ int launch_conv_allco(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_
 // big<4> spills heavily, and conv3x3_bf16_allco_kernel<12, 48> (144 accumulators) needs 256 VGPRs and spills 15 more (64 bytes of
 // scratch per lane, hipcc -Rpass-analysis=kernel-resource-usage; profiles/conv_allco_ab.txt).  In two groups of 96 channels the
 // all-channels kernel holds 72 (8 x 48) or 96 (8 x 64) accumulators: 158 / 201 VGPRs, no scratch (profiles/conv_allco_groups_ab.txt).
-int conv_m0_enabled() {
-    static const int v = env_int("ALSEP_CONV_M0", 1);
-    return v;
-}
-int conv_regw_enabled() {
-    static const int v = env_int("ALSEP_CONV_REGW", 1);
-    return v;
-}
-int conv_big_enabled() {
-    static const int v = env_int("ALSEP_CONV_BIG", 1);
-    return v;
-}
-int conv_mq_enabled() {
-    static const int v = env_int("ALSEP_CONV_MQ", 1);
-    return v;
-}
-int conv_big3_enabled() {
-    static const int v = env_int("ALSEP_CONV_BIG3", 1);
-    return v;
-}
-
-int conv_allco_enabled() {
-    static const int v = env_int("ALSEP_CONV_ALLCO", 1);
-    return v;
-}
+//
+// ds / us
+//   ALSEP_PIX_STREAM  1 (default): a ds / us layer that has a fragment-order image (bf16 / f16, levels 0 <-> 1 <-> 2 <-> 3) runs on the
+//                     streaming kernels where F' % 64 == 0; 0: pix_gemm_kernel.
+//   ALSEP_PIX_PIPE    1 (default) = the ds / us of the middle levels run on ds_pipe_kernel / us_pipe_kernel for the instances in
+//                     kPixPipeRouted (each is routed there only where it measured faster than its stream kernel on the same box:
+//                     profiles/pix_pipe_kernel_stats.txt); 0 = never (the stream kernels, as before); 2 = every instance (measurements, tests).
+//                     ALSEP_PIX_PIPE_GRID=n caps their grid (tests: several tiles per workgroup at small shapes).
+//
+// TDF linears
+//   ALSEP_TDF_WIDE    0 = 128-row kernel only; 1 (default) = wide kernel where M % 192 == 0, 384 rows per workgroup for a
+//                     first linear whose whole M is 384; 4 / 8 = force 192 / 384 rows wherever M allows (experiments, tests)
+//   ALSEP_TDF_YFAST   1 (default): the wide kernel's M / BM row blocks of one column tile run back to back (1-D grid, needs gx % 8 == 0);
+//                     0: the column tile is the fastest grid dimension.
+//   ALSEP_TDF_RPF     2 (default): the wide kernel requests residual rows two units ahead of the stores; 0: residual rows loaded where they
+//                     are used (timing comparison only; such a launch neither folds the final conv nor goes to the persistent kernel).
+//   ALSEP_TDF_FINAL   1 (default) = fold the final 1x1 conv into the last residual TDF launch where the wide 192-row kernel
+//                     serves it and C == 48; 0 = always the separate final_conv_kernel
+//   ALSEP_TDF_PERSIST 1 (default) = the residual linear of levels 0 and 1 runs on tdf_bf16_persist_kernel for the launch kinds
+//                     in kTdfPersistRouted (each kind is routed there only where it measured faster than the wide kernel on the same box:
+//                     profiles/tdf_persist_kernel_stats.txt); 0 = never (the wide kernel, as before); 2 = every kind the kernel serves
+//                     (measurements, tests).  ALSEP_TDF_PERSIST_GRID=n caps its grid (tests: several items per workgroup at small shapes).
+//   ALSEP_TDF_FUSED   1 (default) = the two TDF linears of a block run as one launch of tdf_bf16_fused_kernel at the levels in
+//                     kTdfFusedRouted (a level is routed there only where, in kernel traces of one session, the fused launch's mean and max lay below
+//                     the sum of the two old launches' minima: profiles/tdf_fused_kernel_stats.txt), and only at no fewer items than the level was
+//                     measured at (kTdfFusedFloor: the bench's 52 windows -- 9984 items at F = 768, 3328 at F = 384; below that the workgroups run
+//                     fewer rounds and nothing was measured); 0 = never (two launches of tdf_bf16_kernel, as before); 2 = every shape an instance
+//                     serves (bf16 / f16 on the DMA path, bn = 8, F = 768 or 384, C a multiple of 48 up to 192), without the floor (tests).
+//                     ALSEP_TDF_FUSED_GRID=n caps its grid (tests: several items per workgroup at small shapes).
+struct Switches {
+    int conv_m0, conv_regw, conv_big, conv_mq, conv_big3, conv_allco, conv_allco_tw, conv_allco_grid, conv_nyfast;
+    int pix_stream, pix_pipe, pix_pipe_grid;
+    int tdf_wide, tdf_yfast, tdf_rpf, tdf_final, tdf_persist, tdf_persist_grid, tdf_fused, tdf_fused_grid;
+};
 // Levels that measured faster on conv3x3_bf16_allco_kernel than on their kernel, same box, bench shape (profiles/conv_allco_kernel_stats.txt,
 // conv_allco_ab.txt; c = 192: conv_allco_groups_kernel_stats.txt, conv_allco_groups_ab.txt); only these are routed there by default.
 constexpr int kConvAllco144 = 1, kConvAllco192 = 2;
 constexpr int kConvAllcoRouted = kConvAllco144 | kConvAllco192;
 // the tile width of the instances in output groups (c = 192 / 288): 48 or 64
 constexpr int kConvAllcoTw = 64;
-int conv_allco_tw() {
-    static const int v = env_int("ALSEP_CONV_ALLCO_TW", kConvAllcoTw) == 48 ? 48 : 64;
-    return v;
+enum { kPixPipeDs96 = 1, kPixPipeDs144 = 2, kPixPipeUs192 = 4, kPixPipeUs144 = 8 };
+constexpr int kPixPipeRouted = kPixPipeDs96 | kPixPipeDs144 | kPixPipeUs192 | kPixPipeUs144;
+enum { kTdfPersistK384 = 1, kTdfPersistK192 = 2, kTdfPersistFinal = 4 };
+constexpr int kTdfPersistRouted = kTdfPersistK384 | kTdfPersistK192 | kTdfPersistFinal;
+enum { kTdfFusedF768 = 1, kTdfFusedF384 = 2 };
+constexpr int kTdfFusedRouted = kTdfFusedF768 | kTdfFusedF384;
+constexpr int64_t kTdfFusedFloor[2] = {9984, 3328};
+
+const Switches& switches() {
+    static const Switches s = [] {
+        Switches v;
+        v.conv_m0 = env_int("ALSEP_CONV_M0", 1);
+        v.conv_regw = env_int("ALSEP_CONV_REGW", 1);
+        v.conv_big = env_int("ALSEP_CONV_BIG", 1);
+        v.conv_mq = env_int("ALSEP_CONV_MQ", 1);
+        v.conv_big3 = env_int("ALSEP_CONV_BIG3", 1);
+        v.conv_allco = env_int("ALSEP_CONV_ALLCO", 1);
+        v.conv_allco_tw = env_int("ALSEP_CONV_ALLCO_TW", kConvAllcoTw) == 48 ? 48 : 64;
+        v.conv_allco_grid = env_int("ALSEP_CONV_ALLCO_GRID", 0);
+        v.conv_nyfast = env_int("ALSEP_CONV_NYFAST", 1);
+        v.pix_stream = env_int("ALSEP_PIX_STREAM", 1);
+        v.pix_pipe = env_int("ALSEP_PIX_PIPE", 1);
+        v.pix_pipe_grid = env_int("ALSEP_PIX_PIPE_GRID", 0);
+        v.tdf_wide = env_int("ALSEP_TDF_WIDE", 1);
+        v.tdf_yfast = env_int("ALSEP_TDF_YFAST", 1);
+        v.tdf_rpf = env_int("ALSEP_TDF_RPF", 2);
+        v.tdf_final = env_int("ALSEP_TDF_FINAL", 1);
+        v.tdf_persist = env_int("ALSEP_TDF_PERSIST", 1);
+        v.tdf_persist_grid = env_int("ALSEP_TDF_PERSIST_GRID", 0);
+        v.tdf_fused = env_int("ALSEP_TDF_FUSED", 1);
+        v.tdf_fused_grid = env_int("ALSEP_TDF_FUSED_GRID", 0);
+        return v;
+    }();
+    return s;
+}
+// a switch over a mask of measured kinds (_PIX_PIPE, _TDF_PERSIST): 2 and up = every kind, 1 = the kinds in `routed`, else none
+bool mask_routed(int mode, int routed, int kind) { return mode >= 2 || (mode == 1 && (routed & kind)); }
+
+// ---- routes --------------------------------------------------------------------------------
+// What a route_*() function answers for one layer launch: the kernel instance (K: the enum of the layer kind), the profiling class, and
+// the names the launch is counted under -- `check`, which ALSEP_LAUNCH_CHECK reports and counts, and `also`.  The pinned launch names
+// (bench.py and the tests read them) count LAYER launches, whichever instance serves them: `also` holds the instance's own name where it
+// has one and the pinned names of the kernel it replaces -- an all-channels conv counts under big<3>'s or the plain kernel's names, a
+// persistent TDF launch under the wide kernel's, a fused TDF launch twice under tdf_bf16_kernel (it is two layers).  finish_launch() is
+// the only place that notes them.  A route function launches nothing and touches no ctx.
+template <typename K>
+struct Route {
+    K kernel;
+    int prof_class;
+    const char* check;
+    const char* also[3];
+};
+template <typename K>
+int finish_launch(alsep_ctx* ctx, const Route<K>& r) {
+    for (const char* name : r.also)
+        if (name) note_launch(ctx, name);
+    ALSEP_LAUNCH_CHECK(ctx, r.check);
+    return ALSEP_OK;
+}
+
+// ---- launches ------------------------------------------------------------------------------
+// One kernel launch on ctx->stream; kLdsRaise first raises the kernel's dynamic-LDS limit to `lds` (the launches above 64 KiB).
+enum LdsLimit { kLdsAsIs, kLdsRaise };
+template <typename... P, typename... A>
+hipError_t launch(alsep_ctx* ctx, void (*kern)(P...), dim3 grid, dim3 block, size_t lds, LdsLimit limit, A... args) {
+    static_assert(sizeof...(P) == sizeof...(A), "one argument per kernel parameter");
+    if (limit == kLdsRaise) {
+        const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, grid, block, lds, ctx->stream, static_cast<P>(args)...);
+    return hipSuccess;
+}
+// f(std::true_type) or f(std::false_type): a template instance chosen by a run-time bool, with one argument list
+template <typename F>
+auto dispatch_bool(bool v, F f) {
+    return v ? f(std::true_type()) : f(std::false_type());
+}
+// the grid of a persistent kernel that fills a CU's LDS: one workgroup per CU, at most `cap` (a *_GRID switch; 0 = none), one per item
+unsigned per_cu_grid(alsep_ctx* ctx, int cap, int64_t nitems) {
+    int64_t grid = device_cu_count(ctx);
+    if (cap > 0 && cap < grid) grid = cap;
+    return (unsigned)std::min<int64_t>(grid, nitems);
+}
+
+// work of a 3x3 convolution for the profile: 2 x 9 flops per input channel, output channel and pixel; every activation read and written once
+void conv_work(ProfScope& prof, const ConvLayer& L, size_t elem_bytes, int64_t B, int Th, int Fw) {
+    prof.work(18.0 * (double)L.cin * L.cout * B * Th * Fw, (double)elem_bytes * B * Th * Fw * (L.cin + L.cout));
+}
+
+template <typename T, int KC, int BN, int TW>
+int launch_conv(alsep_ctx* ctx, const ConvLayer& L, const T* X, T* Y, int64_t B, int Th, int Fw) {
+    typedef ConvCfg<T, KC, BN, TW> Cf;
+    const int tiles_t = (int)ceil_div64(Th, Cf::TH), tiles_f = (int)ceil_div64(Fw, TW);
+    const int64_t ntiles = B * tiles_t * tiles_f;
+    if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
+    ProfScope prof(ctx, TW == 64 ? ALSEP_PROF_CONV3X3 : ALSEP_PROF_CONV3X3_SMALL);
+    conv_work(prof, L, sizeof(*X), B, Th, Fw);
+    ALSEP_HIP(ctx, launch(ctx, conv3x3_kernel<T, KC, BN, TW>, dim3((unsigned)ntiles, L.cout / BN), dim3(kThreads), Cf::lds_bytes, kLdsRaise, X, Y,
+                          (const T*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles));
+    ALSEP_LAUNCH_CHECK(ctx, "conv3x3_kernel");
+    return ALSEP_OK;
+}
+
+template <typename T, int KC, int BN>
+int run_conv_tw(alsep_ctx* ctx, const ConvLayer& L, const T* X, T* Y, int64_t B, int Th, int Fw) {
+    if (Fw >= 64 && Fw % 64 == 0) return launch_conv<T, KC, BN, 64>(ctx, L, X, Y, B, Th, Fw);
+    if (Fw >= 32) return launch_conv<T, KC, BN, 32>(ctx, L, X, Y, B, Th, Fw);
+    return launch_conv<T, KC, BN, 16>(ctx, L, X, Y, B, Th, Fw);
+}
+
+// The instances that serve a bf16 / f16 3x3 conv with c % 48 == 0 (L.dma_path), in the order route_conv_dma tries them.
+enum class ConvKernel { M0, Regw48x64, Regw48x32, Regw96, Allco144, Allco192x48, Allco192x64, Allco288x48, Allco288x64, Mq, Big3, Plain64, Plain32, Plain16 };
+typedef Route<ConvKernel> ConvRoute;
+
+ConvRoute route_conv_dma(const Switches& s, const ConvLayer& L, int64_t B, int Th, int Fw) {
+    typedef ConvKernel K;
+    const int c = L.cout;
+    const bool plain64 = Fw >= 64 && Fw % 64 == 0;           // the plain kernel's choice between <64> and <small>
+    const int plain_class = plain64 ? ALSEP_PROF_CONV3X3 : ALSEP_PROF_CONV3X3_SMALL;
+    const char* const plain_name = plain64 ? "conv3x3_bf16_kernel<64>" : "conv3x3_bf16_kernel<small>";
+    if (s.conv_m0 && L.cin == 48 && c == 48 && Th % 8 == 0 && Fw % 48 == 0 && (s.conv_m0 >= 2 || B * (Th / 8) * (Fw / 48) >= 256))
+        return {K::M0, ALSEP_PROF_CONV3X3_REGW, "conv3x3_bf16_m0_kernel", {}};
+    if (s.conv_regw && Th % 4 == 0 && Fw % 64 == 0 && L.cin == c) {
+        const K k = c == 48 ? (s.conv_regw == 3 ? K::Regw48x64 : K::Regw48x32) : K::Regw96;
+        if (c == 48 || (c == 96 && s.conv_regw >= 2)) return {k, ALSEP_PROF_CONV3X3_REGW, "conv3x3_bf16_regw_kernel", {}};
+    }
+    if (s.conv_big && L.cin == c && Th % 8 == 0) {           // the 8-wave kernels
+        // the shapes mq and big<3> take (their tile floor), and the only ones the all-channels instances were measured at
+        const bool big_shape = Fw % 64 == 0 && (s.conv_big >= 2 || B * (Th / 8) * (Fw / 64) >= 96);
+        if (c == 144 && s.conv_big3 && s.conv_allco && Fw % 48 == 0 && (s.conv_allco >= 2 || ((kConvAllcoRouted & kConvAllco144) && big_shape)))
+            return {K::Allco144, ALSEP_PROF_CONV3X3_BIG3, "conv3x3_bf16_allco_kernel", {"conv3x3_bf16_big_kernel", "conv3x3_bf16_big_kernel<3>"}};
+        // in output groups: by default only c = 192; replaces the plain kernel and keeps its profiling class, so that a level's class
+        // does not depend on the instance that serves it
+        const int tw = s.conv_allco_tw;
+        if ((c == 192 || c == 288) && s.conv_allco && Fw % tw == 0 &&
+            (s.conv_allco >= 2 || ((kConvAllcoRouted & kConvAllco192) && c == 192 && big_shape))) {
+            const K k = c == 192 ? (tw == 48 ? K::Allco192x48 : K::Allco192x64) : (tw == 48 ? K::Allco288x48 : K::Allco288x64);
+            return {k, plain_class, "conv3x3_bf16_allco_kernel",
+                    {tw == 48 ? "conv3x3_bf16_allco_kernel<6,48>" : "conv3x3_bf16_allco_kernel<6,64>", "conv3x3_bf16_kernel", plain_name}};
+        }
+        if (big_shape && c == 96 && s.conv_mq) return {K::Mq, ALSEP_PROF_CONV3X3_BIG, "conv3x3_bf16_mq_kernel", {}};
+        if (big_shape && c == 144 && s.conv_big3) return {K::Big3, ALSEP_PROF_CONV3X3_BIG3, "conv3x3_bf16_big_kernel", {"conv3x3_bf16_big_kernel<3>"}};
+    }
+    return {plain64 ? K::Plain64 : Fw >= 32 ? K::Plain32 : K::Plain16, plain_class, "conv3x3_bf16_kernel", {plain_name}};
+}
+
+template <int TW>
+int launch_conv_dma(alsep_ctx* ctx, const ConvRoute& r, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B,
+                    int Th, int Fw) {
+    typedef ConvB16<TW> Cf;
+    const int tiles_t = (int)ceil_div64(Th, Cf::TH), tiles_f = (int)ceil_div64(Fw, TW);
+    const int64_t ntiles = B * tiles_t * tiles_f;
+    if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
+    ProfScope prof(ctx, r.prof_class);
+    conv_work(prof, L, sizeof(*X), B, Th, Fw);
+    const int nyc = L.cout / Cf::BN;
+    const int ny_fastest = switches().conv_nyfast && ntiles % 8 == 0 && nyc > 1 && ntiles * nyc <= 0x7fffffff;
+    ALSEP_HIP(ctx, launch(ctx, conv3x3_bf16_kernel<TW>, ny_fastest ? dim3((unsigned)(ntiles * nyc)) : dim3((unsigned)ntiles, nyc), dim3(kThreads),
+                          Cf::lds_bytes, kLdsRaise, X, Y, (const bf16_t*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page,
+                          Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles, /*ablate*/ 0, /*stagger*/ 0, ny_fastest));
+    return finish_launch(ctx, r);
+}
+
+template <int NQ, int RING_ = 3, int OCC = 1, int TW_ = 64>
+int launch_conv_regw(alsep_ctx* ctx, const ConvRoute& r, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B,
+                     int Th, int Fw) {
+    typedef ConvRW<NQ, RING_, TW_> Cf;
+    const int tiles_t = Th / Cf::TH, tiles_f = Fw / Cf::TW;
+    const int64_t ntiles = B * tiles_t * tiles_f;
+    if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
+    const int ny = L.cout / Cf::BN;
+    int gx = OCC * 256 / ny;                                // OCC workgroups per CU over the whole grid
+    if (gx > ntiles) gx = (int)ntiles;
+    ProfScope prof(ctx, r.prof_class);
+    conv_work(prof, L, sizeof(*X), B, Th, Fw);
+    ALSEP_HIP(ctx, launch(ctx, conv3x3_bf16_regw_kernel<NQ, RING_, OCC, TW_>, dim3((unsigned)gx, ny), dim3(kThreads), Cf::lds_bytes, kLdsRaise, X, Y,
+                          (const bf16_t*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t,
+                          tiles_f, (int)ntiles));
+    return finish_launch(ctx, r);
+}
+
+// The 8-wave persistent convs (conv3x3_bf16_m0_kernel, _mq_kernel, _big_kernel<3>, _allco_kernel) share their argument list and their
+// launch: one workgroup per CU, each walking the tiles blockIdx.x, blockIdx.x + gridDim.x, ...  Cf is the kernel's tile configuration, wimg
+// its weight image; the caller has checked that the layer fits the kernel.
+template <typename Cf, typename Kern>
+int launch_conv_persist(alsep_ctx* ctx, Kern kern, const ConvRoute& r, const ConvLayer& L, const DevBuf& wimg, const bf16_t* X, bf16_t* Y,
+                        const bf16_t* zero_page, int64_t B, int Th, int Fw, int grid_cap = 0) {
+    const int tiles_t = Th / Cf::TH, tiles_f = Fw / Cf::TW;
+    const int64_t ntiles = B * tiles_t * tiles_f;
+    if (ntiles > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
+    int gx = ntiles < 256 ? (int)ntiles : 256;
+    if (grid_cap > 0 && gx > grid_cap) gx = grid_cap;
+    ProfScope prof(ctx, r.prof_class);
+    conv_work(prof, L, sizeof(*X), B, Th, Fw);
+    ALSEP_HIP(ctx, launch(ctx, kern, dim3((unsigned)gx), dim3(kBigThreads), Cf::lds_bytes, kLdsRaise, X, Y, (const bf16_t*)wimg.p,
+                          (const float*)L.scale.p, (const float*)L.shift.p, zero_page, Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles));
+    return finish_launch(ctx, r);
+}
+
+int launch_conv_big3(alsep_ctx* ctx, const ConvRoute& r, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
+    if (!L.w_big.p) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no big-tile weight image for this layer");
+    return launch_conv_persist<ConvBig<3>>(ctx, conv3x3_bf16_big_kernel<3>, r, L, L.w_big, X, Y, zero_page, B, Th, Fw);
+}
+
+int launch_conv_mq(alsep_ctx* ctx, const ConvRoute& r, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
+    if (!L.w_mq.p || L.cout != ConvMq::ROWS || L.cin % ConvMq::KC) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no mq weight image for this layer");
+    return launch_conv_persist<ConvMq>(ctx, conv3x3_bf16_mq_kernel, r, L, L.w_mq, X, Y, zero_page, B, Th, Fw);
+}
+
+int launch_conv_m0(alsep_ctx* ctx, const ConvRoute& r, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
+    if (!L.w_big.p || L.cout != ConvM0::ROWS || L.cin != ConvM0::KC) return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no m0 weight image for this layer");
+    return launch_conv_persist<ConvM0>(ctx, conv3x3_bf16_m0_kernel, r, L, L.w_big, X, Y, zero_page, B, Th, Fw);
+}
+
+// <9, 48, 1> serves c = 144; the instances in output groups, <6, 48 | 64, 2 | 3>, c = 192 / 288
+template <int NM, int TW, int NGRP>
+int launch_conv_allco(alsep_ctx* ctx, const ConvRoute& r, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zero_page, int64_t B, int Th, int Fw) {
+    typedef ConvAllco<NM, TW, NGRP> Cf;
+    static_assert((NM == 9 && TW == 48 && NGRP == 1) || (NM == 6 && NGRP >= 2), "an instance that has a weight image and a route");
+    if (!L.w_ac.p || L.cout != Cf::COUT || L.cin != L.cout || Th % Cf::TH || Fw % TW)
+        return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no all-channels weight image for this layer, or not its shape");
+    return launch_conv_persist<Cf>(ctx, conv3x3_bf16_allco_kernel<NM, TW, NGRP>, r, L, L.w_ac, X, Y, zero_page, B, Th, Fw,
+                                   switches().conv_allco_grid);
 }
 
 int run_conv_dma(alsep_ctx* ctx, const ConvLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* zp, int64_t B, int Th, int Fw) {
-    if (conv_m0_enabled() && L.cin == 48 && L.cout == 48 && Th % 8 == 0 && Fw % 48 == 0 &&
-        (conv_m0_enabled() >= 2 || B * (Th / 8) * (Fw / 48) >= 256))
-        return launch_conv_m0(ctx, L, X, Y, zp, B, Th, Fw);
-    if (conv_regw_enabled() && Th % 4 == 0 && Fw % 64 == 0 && L.cin == L.cout) {
-        if (L.cin == 48 && conv_regw_enabled() == 3) return launch_conv_regw<1>(ctx, L, X, Y, zp, B, Th, Fw);
-        if (L.cin == 48) return launch_conv_regw<1, 3, 2, 32>(ctx, L, X, Y, zp, B, Th, Fw);
-        if (L.cin == 96 && conv_regw_enabled() >= 2) return launch_conv_regw<2>(ctx, L, X, Y, zp, B, Th, Fw);
+    const ConvRoute r = route_conv_dma(switches(), L, B, Th, Fw);
+    switch (r.kernel) {
+    case ConvKernel::M0: return launch_conv_m0(ctx, r, L, X, Y, zp, B, Th, Fw);
+    case ConvKernel::Regw48x64: return launch_conv_regw<1>(ctx, r, L, X, Y, zp, B, Th, Fw);
+    case ConvKernel::Regw48x32: return launch_conv_regw<1, 3, 2, 32>(ctx, r, L, X, Y, zp, B, Th, Fw);
+    case ConvKernel::Regw96: return launch_conv_regw<2>(ctx, r, L, X, Y, zp, B, Th, Fw);
+    case ConvKernel::Allco144: return launch_conv_allco<9, 48, 1>(ctx, r, L, X, Y, zp, B, Th, Fw);
+    case ConvKernel::Allco192x48: return launch_conv_allco<6, 48, 2>(ctx, r, L, X, Y, zp, B, Th, Fw);
+    case ConvKernel::Allco192x64: return launch_conv_allco<6, 64, 2>(ctx, r, L, X, Y, zp, B, Th, Fw);
+    case ConvKernel::Allco288x48: return launch_conv_allco<6, 48, 3>(ctx, r, L, X, Y, zp, B, Th, Fw);
+    case ConvKernel::Allco288x64: return launch_conv_allco<6, 64, 3>(ctx, r, L, X, Y, zp, B, Th, Fw);
+    case ConvKernel::Mq: return launch_conv_mq(ctx, r, L, X, Y, zp, B, Th, Fw);
+    case ConvKernel::Big3: return launch_conv_big3(ctx, r, L, X, Y, zp, B, Th, Fw);
+    case ConvKernel::Plain64: return launch_conv_dma<64>(ctx, r, L, X, Y, zp, B, Th, Fw);
+    case ConvKernel::Plain32: return launch_conv_dma<32>(ctx, r, L, X, Y, zp, B, Th, Fw);
+    case ConvKernel::Plain16: return launch_conv_dma<16>(ctx, r, L, X, Y, zp, B, Th, Fw);
     }
-    if (conv_big_enabled() && conv_big3_enabled() && conv_allco_enabled() && Th % 8 == 0 && Fw % 48 == 0 && L.cin == 144 && L.cout == 144) {
-        const int mode = conv_allco_enabled();
-        // by default only what big<3> served (F % 64 == 0 too, its tile floor): the shapes the routing was measured at
-        const bool big3_shape = Fw % 64 == 0 && (conv_big_enabled() >= 2 || B * (Th / 8) * (Fw / 64) >= 96);
-        if (mode >= 2 || ((kConvAllcoRouted & kConvAllco144) && big3_shape)) return launch_conv_allco<9, 48, 1>(ctx, L, X, Y, zp, B, Th, Fw);
-    }
-    if (conv_big_enabled() && conv_allco_enabled() && L.cin == L.cout && (L.cout == 192 || L.cout == 288)) {
-        const int mode = conv_allco_enabled(), tw = conv_allco_tw();
-        // by default only c = 192, and only where conv3x3_bf16_kernel<64> ran it with the tile floor of the other 8-wave kernels
-        const bool measured_shape = L.cout == 192 && Fw % 64 == 0 && (conv_big_enabled() >= 2 || B * (Th / 8) * (Fw / 64) >= 96);
-        if (Th % 8 == 0 && Fw % tw == 0 && (mode >= 2 || ((kConvAllcoRouted & kConvAllco192) && measured_shape))) {
-            if (L.cout == 192) return tw == 48 ? launch_conv_allco<6, 48, 2>(ctx, L, X, Y, zp, B, Th, Fw) : launch_conv_allco<6, 64, 2>(ctx, L, X, Y, zp, B, Th, Fw);
-            return tw == 48 ? launch_conv_allco<6, 48, 3>(ctx, L, X, Y, zp, B, Th, Fw) : launch_conv_allco<6, 64, 3>(ctx, L, X, Y, zp, B, Th, Fw);
-        }
-    }
-    if (conv_big_enabled() && Th % 8 == 0 && Fw % 64 == 0 && L.cin == L.cout &&
-        (conv_big_enabled() >= 2 || B * (Th / 8) * (Fw / 64) >= 96)) {
-        if (L.cout == 96 && conv_mq_enabled()) return launch_conv_mq(ctx, L, X, Y, zp, B, Th, Fw);
-        if (L.cout == 144 && conv_big3_enabled()) return launch_conv_big3(ctx, L, X, Y, zp, B, Th, Fw);
-    }
-    if (Fw >= 64 && Fw % 64 == 0) return launch_conv_dma<64>(ctx, L, X, Y, zp, B, Th, Fw);
-    if (Fw >= 32) return launch_conv_dma<32>(ctx, L, X, Y, zp, B, Th, Fw);
-    return launch_conv_dma<16>(ctx, L, X, Y, zp, B, Th, Fw);
-}
-int run_conv_dma(alsep_ctx* ctx, const ConvLayer&, const float*, float*, const float*, int64_t, int, int) {
-    return alsep_fail(ctx, ALSEP_ERR_STATE, "LDS-DMA conv path is bf16 only");
+    return alsep_fail(ctx, ALSEP_ERR_STATE, "conv3x3: no such route");
 }
 
 #ifndef ALSEP_F16_TU
@@ -3110,15 +3178,12 @@ int launch_conv_split(alsep_ctx* ctx, const ConvLayer& L, const float* X, float*
     const int64_t ntiles = B * tiles_t * tiles_f;
     const int nyc = L.cout / BN;
     if (ntiles * nyc > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "conv3x3: too many tiles");
-    ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)conv3x3_f32s_kernel<KC, BN, TW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)Cf::lds_bytes));
     ProfScope prof(ctx, TW >= 32 ? ALSEP_PROF_CONV3X3 : ALSEP_PROF_CONV3X3_SMALL);
     conv_work(prof, L, 4, B, Th, Fw);
     const int nyf = (ntiles % 8 == 0 && nyc > 1) ? 1 : 0;
     const dim3 grid = nyf ? dim3((unsigned)(ntiles * nyc)) : dim3((unsigned)ntiles, nyc);
-    hipLaunchKernelGGL((conv3x3_f32s_kernel<KC, BN, TW>), grid, dim3(kThreads), Cf::lds_bytes, ctx->stream, X, Y,
-                       (const hs_t*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, Th, Fw, L.cin, L.cout, tiles_t, tiles_f,
-                       (int)ntiles, nyf, L.range_flag);
+    ALSEP_HIP(ctx, launch(ctx, conv3x3_f32s_kernel<KC, BN, TW>, grid, dim3(kThreads), Cf::lds_bytes, kLdsRaise, X, Y, (const hs_t*)L.w.p,
+                          (const float*)L.scale.p, (const float*)L.shift.p, Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles, nyf, L.range_flag));
     ALSEP_LAUNCH_CHECK(ctx, "conv3x3_f32s_kernel");
     return ALSEP_OK;
 }
@@ -3130,121 +3195,81 @@ int run_conv_split_tw(alsep_ctx* ctx, const ConvLayer& L, const float* X, float*
 int run_conv_split(alsep_ctx* ctx, const ConvLayer& L, const float* X, float* Y, int64_t B, int Th, int Fw) {
     return L.split == 24 ? run_conv_split_tw<24, 48>(ctx, L, X, Y, B, Th, Fw) : run_conv_split_tw<16, 16>(ctx, L, X, Y, B, Th, Fw);
 }
-int run_conv_split(alsep_ctx* ctx, const ConvLayer&, const bf16_t*, bf16_t*, int64_t, int, int) {
-    return alsep_fail(ctx, ALSEP_ERR_STATE, "split contraction is a float32 mode");
-}
 #endif
 
+// make_conv sets `split` only in a float32 network and `dma_path` only in a bf16 / f16 one (and make_block / build_net the TDF and
+// ds / us images -- dma_path, wwide, wfused, wfrag -- likewise), so each storage type compiles only the paths it can take.
 template <typename T>
 int run_conv(alsep_ctx* ctx, const ConvLayer& L, const T* X, T* Y, int64_t B, int Th, int Fw, const void* zero_page) {
+    if constexpr (std::is_same<T, float>::value) {
 #ifndef ALSEP_F16_TU
-    if (L.split) return run_conv_split(ctx, L, X, Y, B, Th, Fw);
+        if (L.split) return run_conv_split(ctx, L, X, Y, B, Th, Fw);
 #endif
-    if (L.dma_path) return run_conv_dma(ctx, L, X, Y, (const T*)zero_page, B, Th, Fw);
+    } else {
+        if (L.dma_path) return run_conv_dma(ctx, L, X, Y, (const T*)zero_page, B, Th, Fw);
+    }
     if (conv_uses_main<T>(L.cin, L.cout)) return run_conv_tw<T, ConvSel<T>::KC, ConvSel<T>::BN>(ctx, L, X, Y, B, Th, Fw);
     return run_conv_tw<T, ConvSel16<T>::KC, ConvSel16<T>::BN>(ctx, L, X, Y, B, Th, Fw);
 }
 
-int pix_stream_enabled() {
-    static const int v = env_int("ALSEP_PIX_STREAM", 1);
-    return v;
+// The instances that serve a ds / us layer on the stream path (L.wfrag): the pipelined kernels of the middle levels, the stream kernels
+enum class PixKernel { DsPipe96, DsPipe144, UsPipe192, UsPipe144, Ds48, DsSplit96, DsSplit144, Us96, Us144, Us192 };
+typedef Route<PixKernel> PixRoute;
+
+PixRoute route_pix_stream(const Switches& s, int mode, const GemmLayer& L) {
+    typedef PixKernel K;
+    const int cls = ALSEP_PROF_PIX;
+    const char* const chk = "pix stream kernel";
+    const auto pipe = [&](int kind) { return mask_routed(s.pix_pipe, kPixPipeRouted, kind); };
+    if (mode == PIX_DS) {
+        const char* const any = "ds_stream_kernel";
+        if (L.M == DsSplitCfg<96>::M && pipe(kPixPipeDs96)) return {K::DsPipe96, cls, chk, {any, "ds_split_stream_kernel<96>", "ds_pipe_kernel<96>"}};
+        if (L.M == DsSplitCfg<144>::M && pipe(kPixPipeDs144)) return {K::DsPipe144, cls, chk, {any, "ds_split_stream_kernel<144>", "ds_pipe_kernel<144>"}};
+        if (L.M == Ds48::M) return {K::Ds48, cls, chk, {any, "ds48_stream_kernel"}};                                      // 48 -> 96
+        if (L.M == DsSplitCfg<96>::M) return {K::DsSplit96, cls, chk, {any, "ds_split_stream_kernel<96>"}};                // 96 -> 144
+        return {K::DsSplit144, cls, chk, {any, "ds_split_stream_kernel<144>"}};                                            // 144 -> 192
+    }
+    const char* const any = "us_stream_kernel";
+    if (L.K == 192 && pipe(kPixPipeUs192)) return {K::UsPipe192, cls, chk, {any, "us_stream_kernel<192,144>", "us_pipe_kernel<192,144>"}};
+    if (L.K == 144 && pipe(kPixPipeUs144)) return {K::UsPipe144, cls, chk, {any, "us_stream_kernel<144,96>", "us_pipe_kernel<144,96>"}};
+    if (L.K == 96) return {K::Us96, cls, chk, {any, "us_stream_kernel<96,48>"}};                  // 96 -> 48
+    if (L.K == 144) return {K::Us144, cls, chk, {any, "us_stream_kernel<144,96>"}};               // 144 -> 96: 32-pixel tiles, two workgroups per CU
+    return {K::Us192, cls, chk, {any, "us_stream_kernel<192,144>"}};                              // 192 -> 144: 32-pixel tiles (accumulators beside 54 fragments)
 }
-// ALSEP_PIX_PIPE: 1 (default) = the ds / us of the middle levels run on ds_pipe_kernel / us_pipe_kernel for the instances in
-// kPixPipeRouted (each is routed there only where it measured faster than its stream kernel on the same box:
-// profiles/pix_pipe_kernel_stats.txt); 0 = never (the stream kernels, as before); 2 = every instance (measurements, tests).
-// ALSEP_PIX_PIPE_GRID=n caps their grid (tests: several tiles per workgroup at small shapes).
-enum { kPixPipeDs96 = 1, kPixPipeDs144 = 2, kPixPipeUs192 = 4, kPixPipeUs144 = 8 };
-constexpr int kPixPipeRouted = kPixPipeDs96 | kPixPipeDs144 | kPixPipeUs192 | kPixPipeUs144;
-bool pix_pipe_routed(int kind) {
-    static const int v = env_int("ALSEP_PIX_PIPE", 1);
-    return v >= 2 || (v == 1 && (kPixPipeRouted & kind));
-}
-unsigned pix_pipe_grid(alsep_ctx* ctx, int64_t ntile) {     // more than 128 KiB of LDS: one workgroup per CU
-    static const int cap = env_int("ALSEP_PIX_PIPE_GRID", 0);
-    int64_t grid = device_cu_count(ctx);
-    if (cap > 0 && cap < grid) grid = cap;
-    return (unsigned)std::min<int64_t>(grid, ntile);
-}
-template <int C_, int PX_, int D_>
-hipError_t launch_ds_pipe(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t* Y, int64_t ncols, int Tp, int Fp) {
-    typedef DsPipeCfg<C_, PX_, D_> P;
-    const hipError_t e = hipFuncSetAttribute((const void*)ds_pipe_kernel<C_, PX_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P::lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((ds_pipe_kernel<C_, PX_, D_>), dim3(pix_pipe_grid(ctx, ncols / P::PX)), dim3(kThreads), P::lds_bytes, ctx->stream, X, Y,
-                       (const bf16_t*)L.wfrag.p, (const float*)L.scale.p, (const float*)L.shift.p, ncols, Tp, Fp);
-    return hipSuccess;
-}
-template <int CIN, int C2_, int NI_, int D_>
-hipError_t launch_us_pipe(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* skip, int64_t ncols, int Tp, int Fp) {
-    typedef UsPipeCfg<CIN, C2_, NI_, D_> P;
-    const hipError_t e = hipFuncSetAttribute((const void*)us_pipe_kernel<CIN, C2_, NI_, D_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P::lds_bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((us_pipe_kernel<CIN, C2_, NI_, D_>), dim3(pix_pipe_grid(ctx, ncols / P::PX)), dim3(kThreads), P::lds_bytes, ctx->stream, X, Y,
-                       (const bf16_t*)L.wfrag.p, (const float*)L.scale.p, (const float*)L.shift.p, skip, ncols, Tp, Fp);
-    return hipSuccess;
-}
+
 int run_pix_stream(alsep_ctx* ctx, int mode, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* skip, int64_t ncols,
                    int Tp, int Fp) {
-    ProfScope prof(ctx, ALSEP_PROF_PIX);
+    typedef PixKernel K;
+    const Switches& s = switches();
+    const PixRoute r = route_pix_stream(s, mode, L);
+    ProfScope prof(ctx, r.prof_class);
     const int64_t ntile = ncols / 64;
-    // the pipelined kernels: one more launch-count name each, the pinned names below are noted as before
-    if (mode == PIX_DS && L.M == DsSplitCfg<96>::M && pix_pipe_routed(kPixPipeDs96)) {
-        ALSEP_HIP(ctx, (launch_ds_pipe<96, 64, 1>(ctx, L, X, Y, ncols, Tp, Fp)));
-        note_launch(ctx, "ds_pipe_kernel<96>");
-        note_launch(ctx, "ds_split_stream_kernel<96>");
-    } else if (mode == PIX_DS && L.M == DsSplitCfg<144>::M && pix_pipe_routed(kPixPipeDs144)) {
-        ALSEP_HIP(ctx, (launch_ds_pipe<144, 32, 2>(ctx, L, X, Y, ncols, Tp, Fp)));
-        note_launch(ctx, "ds_pipe_kernel<144>");
-        note_launch(ctx, "ds_split_stream_kernel<144>");
-    } else if (mode != PIX_DS && L.K == 192 && pix_pipe_routed(kPixPipeUs192)) {
-        ALSEP_HIP(ctx, (launch_us_pipe<192, 144, 2, 1>(ctx, L, X, Y, skip, ncols, Tp, Fp)));
-        note_launch(ctx, "us_pipe_kernel<192,144>");
-        note_launch(ctx, "us_stream_kernel<192,144>");
-    } else if (mode != PIX_DS && L.K == 144 && pix_pipe_routed(kPixPipeUs144)) {
-        ALSEP_HIP(ctx, (launch_us_pipe<144, 96, 2, 2>(ctx, L, X, Y, skip, ncols, Tp, Fp)));
-        note_launch(ctx, "us_pipe_kernel<144,96>");
-        note_launch(ctx, "us_stream_kernel<144,96>");
-    } else if (mode == PIX_DS && L.M == Ds48::M) {
-        const size_t lds = 4 * 64 * Ds48::MS * sizeof(bf16_t);
-        const int64_t gx = std::min<int64_t>(ceil_div64(ntile, 4), 256);
-        hipLaunchKernelGGL(ds48_stream_kernel, dim3((unsigned)gx), dim3(kThreads), lds, ctx->stream, X, Y, (const bf16_t*)L.wfrag.p,
-                           (const float*)L.scale.p, (const float*)L.shift.p, ncols, Tp, Fp);
-        note_launch(ctx, "ds48_stream_kernel");
-    } else if (mode == PIX_DS && L.M == DsSplitCfg<96>::M) { // 96 -> 144
-        const size_t lds = 64 * DsSplitCfg<96>::MS * sizeof(bf16_t);
-        const int64_t gx = std::min<int64_t>(ntile, 512);
-        hipLaunchKernelGGL((ds_split_stream_kernel<96, 2>), dim3((unsigned)gx), dim3(kThreads), lds, ctx->stream, X, Y,
-                           (const bf16_t*)L.wfrag.p, (const float*)L.scale.p, (const float*)L.shift.p, ncols, Tp, Fp);
-        note_launch(ctx, "ds_split_stream_kernel<96>");
-    } else if (mode == PIX_DS) {                             // 144 -> 192
-        const size_t lds = 64 * DsSplitCfg<144>::MS * sizeof(bf16_t);
-        const int64_t gx = std::min<int64_t>(ntile, 512);
-        hipLaunchKernelGGL((ds_split_stream_kernel<144, 1>), dim3((unsigned)gx), dim3(kThreads), lds, ctx->stream, X, Y,
-                           (const bf16_t*)L.wfrag.p, (const float*)L.scale.p, (const float*)L.shift.p, ncols, Tp, Fp);
-        note_launch(ctx, "ds_split_stream_kernel<144>");
-    } else {
-#define ALSEP_US(CIN_, C2_, NI_, OCC_, GX_)                                                                                 \
-    {                                                                                                                       \
-        typedef UsCfg<CIN_, C2_, NI_> U;                                                                                    \
-        ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)us_stream_kernel<CIN_, C2_, NI_, OCC_>,                             \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)U::lds_bytes));                 \
-        const int64_t gx = std::min<int64_t>(ncols / U::PX, GX_);                                                           \
-        hipLaunchKernelGGL((us_stream_kernel<CIN_, C2_, NI_, OCC_>), dim3((unsigned)gx), dim3(kThreads), U::lds_bytes,      \
-                           ctx->stream, X, Y, (const bf16_t*)L.wfrag.p, (const float*)L.scale.p, (const float*)L.shift.p,   \
-                           skip, ncols, Tp, Fp);                                                                            \
-        note_launch(ctx, "us_stream_kernel<" #CIN_ "," #C2_ ">");                                                          \
+    const bf16_t* const w = (const bf16_t*)L.wfrag.p;
+    const float* const sc = (const float*)L.scale.p;
+    const float* const sh = (const float*)L.shift.p;
+    // every ds kernel takes the first argument list, every us kernel the second
+    const auto ds = [&](auto kern, int64_t gx, size_t lds, LdsLimit limit) {
+        return launch(ctx, kern, dim3((unsigned)gx), dim3(kThreads), lds, limit, X, Y, w, sc, sh, ncols, Tp, Fp);
+    };
+    const auto us = [&](auto kern, int64_t gx, size_t lds) {
+        return launch(ctx, kern, dim3((unsigned)gx), dim3(kThreads), lds, kLdsRaise, X, Y, w, sc, sh, skip, ncols, Tp, Fp);
+    };
+    const auto pipe_grid = [&](int px) { return per_cu_grid(ctx, s.pix_pipe_grid, ncols / px); };   // more than 128 KiB of LDS
+    hipError_t e = hipSuccess;
+    switch (r.kernel) {
+    case K::DsPipe96: e = ds(ds_pipe_kernel<96, 64, 1>, pipe_grid(DsPipeCfg<96, 64, 1>::PX), DsPipeCfg<96, 64, 1>::lds_bytes, kLdsRaise); break;
+    case K::DsPipe144: e = ds(ds_pipe_kernel<144, 32, 2>, pipe_grid(DsPipeCfg<144, 32, 2>::PX), DsPipeCfg<144, 32, 2>::lds_bytes, kLdsRaise); break;
+    case K::UsPipe192: e = us(us_pipe_kernel<192, 144, 2, 1>, pipe_grid(UsPipeCfg<192, 144, 2, 1>::PX), UsPipeCfg<192, 144, 2, 1>::lds_bytes); break;
+    case K::UsPipe144: e = us(us_pipe_kernel<144, 96, 2, 2>, pipe_grid(UsPipeCfg<144, 96, 2, 2>::PX), UsPipeCfg<144, 96, 2, 2>::lds_bytes); break;
+    case K::Ds48: e = ds(ds48_stream_kernel, std::min<int64_t>(ceil_div64(ntile, 4), 256), 4 * 64 * Ds48::MS * sizeof(bf16_t), kLdsAsIs); break;
+    case K::DsSplit96: e = ds(ds_split_stream_kernel<96, 2>, std::min<int64_t>(ntile, 512), 64 * DsSplitCfg<96>::MS * sizeof(bf16_t), kLdsAsIs); break;
+    case K::DsSplit144: e = ds(ds_split_stream_kernel<144, 1>, std::min<int64_t>(ntile, 512), 64 * DsSplitCfg<144>::MS * sizeof(bf16_t), kLdsAsIs); break;
+    case K::Us96: e = us(us_stream_kernel<96, 48, 4, 1>, std::min<int64_t>(ncols / UsCfg<96, 48, 4>::PX, 512), UsCfg<96, 48, 4>::lds_bytes); break;
+    case K::Us144: e = us(us_stream_kernel<144, 96, 2, 2>, std::min<int64_t>(ncols / UsCfg<144, 96, 2>::PX, 512), UsCfg<144, 96, 2>::lds_bytes); break;
+    case K::Us192: e = us(us_stream_kernel<192, 144, 2, 1>, std::min<int64_t>(ncols / UsCfg<192, 144, 2>::PX, 256), UsCfg<192, 144, 2>::lds_bytes); break;
     }
-        if (L.K == 96) ALSEP_US(96, 48, 4, 1, 512)               // 96 -> 48
-        else if (L.K == 144) ALSEP_US(144, 96, 2, 2, 512)        // 144 -> 96: 32-pixel tiles, two workgroups per CU
-        else ALSEP_US(192, 144, 2, 1, 256)                       // 192 -> 144: 32-pixel tiles (accumulators beside 54 fragments)
-#undef ALSEP_US
-    }
-    note_launch(ctx, mode == PIX_DS ? "ds_stream_kernel" : "us_stream_kernel");
-    ALSEP_LAUNCH_CHECK(ctx, "pix stream kernel");
-    return ALSEP_OK;
-}
-int run_pix_stream(alsep_ctx* ctx, int, const GemmLayer&, const float*, float*, const float*, int64_t, int, int) {
-    return alsep_fail(ctx, ALSEP_ERR_STATE, "streaming ds/us path is bf16 only");
+    ALSEP_HIP(ctx, e);
+    return finish_launch(ctx, r);
 }
 
 #ifndef ALSEP_F16_TU
@@ -3253,19 +3278,14 @@ int run_pix_split(alsep_ctx* ctx, const GemmLayer& L, const float* X, float* Y, 
     typedef GemmSCfg Gc;
     const int64_t gx = ceil_div64(ncols, Gc::BC);
     if (gx > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "pix_gemm: too many column tiles");
-    ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)pix_gemm_f32s_kernel<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gc::lds_bytes));
     ProfScope prof(ctx, ALSEP_PROF_PIX);
     const int nrb = L.Mp / Gc::BR;
     const int fast = (nrb > 1 && gx % 8 == 0 && gx * nrb <= 0x7fffffff) ? nrb : 0;
-    hipLaunchKernelGGL((pix_gemm_f32s_kernel<MODE>), fast ? dim3((unsigned)(gx * nrb)) : dim3((unsigned)gx, nrb), dim3(kThreads), Gc::lds_bytes,
-                       ctx->stream, X, Y, (const hs_t*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, skip, L.M, L.Mp, L.K, L.Kp, ncols,
-                       Tp, Fp, C, C2, L.range_flag, fast);
+    ALSEP_HIP(ctx, launch(ctx, pix_gemm_f32s_kernel<MODE>, fast ? dim3((unsigned)(gx * nrb)) : dim3((unsigned)gx, nrb), dim3(kThreads), Gc::lds_bytes,
+                          kLdsRaise, X, Y, (const hs_t*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, skip, L.M, L.Mp, L.K, L.Kp, ncols,
+                          Tp, Fp, C, C2, L.range_flag, fast));
     ALSEP_LAUNCH_CHECK(ctx, "pix_gemm_f32s_kernel");
     return ALSEP_OK;
-}
-template <int MODE>
-int run_pix_split(alsep_ctx* ctx, const GemmLayer&, const bf16_t*, bf16_t*, const bf16_t*, int64_t, int, int, int, int) {
-    return alsep_fail(ctx, ALSEP_ERR_STATE, "split contraction is a float32 mode");
 }
 int run_tdf_split(alsep_ctx* ctx, const GemmLayer& L, const float* X, float* Y, const float* R, int64_t BT, int C) {
     typedef GemmSCfg Gc;
@@ -3277,48 +3297,38 @@ int run_tdf_split(alsep_ctx* ctx, const GemmLayer& L, const float* X, float* Y, 
     const int nrb = L.Mp / Gc::BR;
     const int fast = (nrb > 1 && gx % 8 == 0 && gx * nrb <= 0x7fffffff) ? nrb : 0;
     const dim3 grid = fast ? dim3((unsigned)(gx * nrb)) : dim3((unsigned)gx, nrb);
-    if (R) {
-        ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)tdf_gemm_f32s_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gc::lds_bytes));
-        hipLaunchKernelGGL((tdf_gemm_f32s_kernel<true>), grid, dim3(kThreads), Gc::lds_bytes, ctx->stream, X, Y, (const hs_t*)L.w.p, bias,
-                           (const float*)L.scale.p, (const float*)L.shift.p, R, L.M, L.Mp, L.K, L.Kp, nunits, C, L.range_flag, fast);
-    } else {
-        ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)tdf_gemm_f32s_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Gc::lds_bytes));
-        hipLaunchKernelGGL((tdf_gemm_f32s_kernel<false>), grid, dim3(kThreads), Gc::lds_bytes, ctx->stream, X, Y, (const hs_t*)L.w.p, bias,
-                           (const float*)L.scale.p, (const float*)L.shift.p, R, L.M, L.Mp, L.K, L.Kp, nunits, C, L.range_flag, fast);
-    }
+    const hipError_t e = dispatch_bool(R != nullptr, [&](auto res) {
+        return launch(ctx, tdf_gemm_f32s_kernel<decltype(res)::value>, grid, dim3(kThreads), Gc::lds_bytes, kLdsRaise, X, Y, (const hs_t*)L.w.p,
+                      bias, (const float*)L.scale.p, (const float*)L.shift.p, R, L.M, L.Mp, L.K, L.Kp, nunits, C, L.range_flag, fast);
+    });
+    ALSEP_HIP(ctx, e);
     ALSEP_LAUNCH_CHECK(ctx, "tdf_gemm_f32s_kernel");
     return ALSEP_OK;
-}
-int run_tdf_split(alsep_ctx* ctx, const GemmLayer&, const bf16_t*, bf16_t*, const bf16_t*, int64_t, int) {
-    return alsep_fail(ctx, ALSEP_ERR_STATE, "split contraction is a float32 mode");
 }
 #endif
 
 template <typename T, int MODE>
 int run_pix(alsep_ctx* ctx, const GemmLayer& L, const T* X, T* Y, const T* skip, int64_t ncols, int Tp, int Fp, int C, int C2) {
     typedef GemmCfg<T> Gc;
+    if constexpr (std::is_same<T, float>::value) {
 #ifndef ALSEP_F16_TU
-    if (L.split) return run_pix_split<MODE>(ctx, L, X, Y, skip, ncols, Tp, Fp, C, C2);
+        if (L.split) return run_pix_split<MODE>(ctx, L, X, Y, skip, ncols, Tp, Fp, C, C2);
 #endif
-    if (L.wfrag.p && pix_stream_enabled() && Fp % 64 == 0) return run_pix_stream(ctx, MODE, L, X, Y, skip, ncols, Tp, Fp);
+    } else {
+        if (L.wfrag.p && switches().pix_stream && Fp % 64 == 0) return run_pix_stream(ctx, MODE, L, X, Y, skip, ncols, Tp, Fp);
+    }
     const int64_t gx = ceil_div64(ncols, Gc::BC);
     if (gx > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "pix_gemm: too many column tiles");
     ProfScope prof(ctx, ALSEP_PROF_PIX);
-    hipLaunchKernelGGL((pix_gemm_kernel<T, MODE>), dim3((unsigned)gx, L.Mp / Gc::BR), dim3(kThreads), Gc::lds_bytes,
-                       ctx->stream, X, Y, (const T*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, skip,
-                       L.M, L.K, L.Kp, ncols, Tp, Fp, C, C2);
+    ALSEP_HIP(ctx, launch(ctx, pix_gemm_kernel<T, MODE>, dim3((unsigned)gx, L.Mp / Gc::BR), dim3(kThreads), Gc::lds_bytes, kLdsAsIs, X, Y,
+                          (const T*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, skip, L.M, L.K, L.Kp, ncols, Tp, Fp, C, C2));
     ALSEP_LAUNCH_CHECK(ctx, "pix_gemm_kernel");
     return ALSEP_OK;
 }
 
-// ALSEP_TDF_WIDE: 0 = 128-row kernel only; 1 (default) = wide kernel where M % 192 == 0, 384 rows per workgroup for a
-// first linear whose whole M is 384; 4 / 8 = force 192 / 384 rows wherever M allows (experiments, tests)
-int tdf_wide_mode() {
-    static const int v = env_int("ALSEP_TDF_WIDE", 1);
-    return v;
-}
 // The final 1x1 convolution of a forward, offered to the last residual TDF launch (run_block's `fin`): the launcher that
-// can fold it (tdf_bf16_wide_kernel<4, true, RPF, FINAL>) sets `done`, and forward_impl() then skips final_conv_kernel.
+// can fold it (tdf_bf16_wide_kernel<4, true, RPF, FINAL>, tdf_bf16_persist_kernel<NT, FINAL>) sets `done`, and forward_impl() then skips
+// final_conv_kernel.
 struct FinalFold {
     const float* w;
     const float* b;
@@ -3326,210 +3336,179 @@ struct FinalFold {
     float alpha;
     bool done;
 };
-// ALSEP_TDF_FINAL: 1 (default) = fold the final 1x1 conv into the last residual TDF launch where the wide 192-row kernel
-// serves it and C == 48; 0 = always the separate final_conv_kernel
-int tdf_final_mode() {
-    static const int v = env_int("ALSEP_TDF_FINAL", 1);
-    return v;
-}
-// ALSEP_TDF_PERSIST: 1 (default) = the residual linear of levels 0 and 1 runs on tdf_bf16_persist_kernel for the launch kinds
-// in kTdfPersistRouted (each kind is routed there only where it measured faster than the wide kernel on the same box:
-// profiles/tdf_persist_kernel_stats.txt); 0 = never (the wide kernel, as before); 2 = every kind the kernel serves
-// (measurements, tests).  ALSEP_TDF_PERSIST_GRID=n caps its grid (tests: several items per workgroup at small shapes).
-enum { kTdfPersistK384 = 1, kTdfPersistK192 = 2, kTdfPersistFinal = 4 };
-constexpr int kTdfPersistRouted = kTdfPersistK384 | kTdfPersistK192 | kTdfPersistFinal;
-int tdf_persist_mode() {
-    static const int v = env_int("ALSEP_TDF_PERSIST", 1);
-    return v;
-}
-template <int NT, bool FINAL>
-void launch_tdf_persist_inst(alsep_ctx* ctx, hipError_t& attr, unsigned grid, const GemmLayer& L, const bf16_t* X, bf16_t* Y,
-                             const bf16_t* R, int64_t nitems, int C, const FinalFold* fin) {
-    constexpr int lds = (int)TdfPersist::lds_bytes(NT, FINAL);
-    attr = hipFuncSetAttribute((const void*)tdf_bf16_persist_kernel<NT, FINAL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (attr != hipSuccess) return;
-    hipLaunchKernelGGL((tdf_bf16_persist_kernel<NT, FINAL>), dim3(grid), dim3(TdfPersist::THREADS), lds, ctx->stream, X, Y,
-                       (const bf16_t*)L.wwide.p, L.has_bias ? (const float*)L.bias.p : nullptr, (const float*)L.scale.p,
-                       (const float*)L.shift.p, R, L.M, nitems, C, fin ? fin->w : nullptr, fin ? fin->b : nullptr,
-                       fin ? (bf16_t*)fin->out : nullptr, fin ? fin->alpha : 0.f);
-}
-// caller: R != nullptr, M % 384 == 0, K 384 or 192, C 48 or 96, nunits % 4 == 0, inside its ProfScope; fin only where C == 48
-int launch_tdf_persist(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* R, int64_t nunits, int C,
-                       FinalFold* fin) {
-    static const int cap = env_int("ALSEP_TDF_PERSIST_GRID", 0);
-    const int64_t nitems = nunits / TdfPersist::UN;
-    int64_t grid = device_cu_count(ctx);                             // 156.75 KiB of LDS: one workgroup per CU
-    if (cap > 0 && cap < grid) grid = cap;
-    if (nitems < grid) grid = nitems;
-    hipError_t attr = hipSuccess;
-    if (fin && L.K == 384) launch_tdf_persist_inst<6, true>(ctx, attr, (unsigned)grid, L, X, Y, R, nitems, C, fin);
-    else if (fin) launch_tdf_persist_inst<3, true>(ctx, attr, (unsigned)grid, L, X, Y, R, nitems, C, fin);
-    else if (L.K == 384) launch_tdf_persist_inst<6, false>(ctx, attr, (unsigned)grid, L, X, Y, R, nitems, C, nullptr);
-    else launch_tdf_persist_inst<3, false>(ctx, attr, (unsigned)grid, L, X, Y, R, nitems, C, nullptr);
-    ALSEP_HIP(ctx, attr);
-    if (fin) {
-        fin->done = true;
-        note_launch(ctx, "tdf_bf16_wide_kernel<res,final>");
+
+// The instances that serve one TDF linear of a bf16 / f16 network with c % 48 == 0 (L.dma_path).  Wide<WM>: Nores = no residual,
+// Res = residual rows requested ahead, Rpf0 = residual rows loaded where they are used, Final = Res with the final 1x1 conv folded in.
+enum class TdfKernel { Plain, Wide4Nores, Wide4Res, Wide4Rpf0, Wide4Final, Wide8Nores, Wide8Res, Wide8Rpf0,
+                       Persist384, Persist192, Persist384Final, Persist192Final };
+typedef Route<TdfKernel> TdfRoute;
+
+// residual: the launch adds R; final_offered: the caller offers the final 1x1 conv (FinalFold); nunits = B T (C / 48)
+TdfRoute route_tdf_dma(const Switches& s, const GemmLayer& L, bool residual, bool final_offered, int64_t nunits, int C) {
+    typedef TdfKernel K;
+    typedef TdfWide<4> W4;
+    const int cls = ALSEP_PROF_TDF;
+    const char* const wide = "tdf_bf16_wide_kernel";
+    const char* const persist = "tdf_bf16_persist_kernel";
+    const char* const res = "tdf_bf16_wide_kernel<res>";
+    if (!(L.wwide.p && s.tdf_wide && L.K % 64 == 0 && nunits % 4 == 0)) return {K::Plain, cls, "tdf_bf16_kernel", {}};
+    const bool can8 = L.M % 384 == 0;
+    const bool use8 = s.tdf_wide == 8 ? can8 : (s.tdf_wide == 4 ? false : (can8 && L.M == 384 && !residual));
+    if (!residual) return {use8 ? K::Wide8Nores : K::Wide4Nores, cls, wide, {"tdf_bf16_wide_kernel<nores>"}};
+    if (s.tdf_rpf == 0) return {use8 ? K::Wide8Rpf0 : K::Wide4Rpf0, cls, wide, {res}};
+    if (use8) return {K::Wide8Res, cls, wide, {res}};
+    const bool fold = final_offered && C == W4::UC && s.tdf_final;
+    if (s.tdf_wide == 1 && L.M % TdfPersist::BM == 0 && (C == W4::UC || C == 2 * W4::UC) && (L.K == 384 || L.K == 192)) {
+        const int kind = fold ? kTdfPersistFinal : (L.K == 384 ? kTdfPersistK384 : kTdfPersistK192);
+        if (mask_routed(s.tdf_persist, kTdfPersistRouted, kind)) {
+            if (fold) return {L.K == 384 ? K::Persist384Final : K::Persist192Final, cls, persist, {res, "tdf_bf16_wide_kernel<res,final>"}};
+            return {L.K == 384 ? K::Persist384 : K::Persist192, cls, persist, {res}};
+        }
     }
-    note_launch(ctx, "tdf_bf16_wide_kernel<res>");                   // one per layer launch, whichever instance serves it
-    ALSEP_LAUNCH_CHECK(ctx, "tdf_bf16_persist_kernel");
-    return ALSEP_OK;
+    if (fold) return {K::Wide4Final, cls, wide, {res, "tdf_bf16_wide_kernel<res,final>"}};
+    return {K::Wide4Res, cls, wide, {res}};
 }
 
-template <int WM>
-int launch_tdf_wide(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* R, int64_t nunits, int C,
+int launch_tdf_plain(alsep_ctx* ctx, const TdfRoute& r, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* R, const bf16_t* zp,
+                     int64_t nunits, int C) {
+    typedef TdfB16 Tc;
+    const float* bias = L.has_bias ? (const float*)L.bias.p : nullptr;
+    ProfScope prof(ctx, r.prof_class);
+    const dim3 grid((unsigned)ceil_div64(nunits, Tc::UN), L.Mp / Tc::BM);
+    const hipError_t e = dispatch_bool(R != nullptr, [&](auto res) {
+        return launch(ctx, tdf_bf16_kernel<decltype(res)::value>, grid, dim3(kThreads), Tc::lds_bytes, kLdsAsIs, X, Y, (const bf16_t*)L.w.p, bias,
+                      (const float*)L.scale.p, (const float*)L.shift.p, R, zp, L.M, L.K, L.Kp, nunits, C);
+    });
+    ALSEP_HIP(ctx, e);
+    return finish_launch(ctx, r);
+}
+
+// fin: FINAL only (where C == 48)
+template <int WM, bool RES, int RPF, bool FINAL>
+int launch_tdf_wide(alsep_ctx* ctx, const TdfRoute& r, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* R, int64_t nunits, int C,
                     FinalFold* fin) {
     typedef TdfWide<WM> Tc;
     const int64_t gx = ceil_div64(nunits, Tc::UN);
-    if (gx > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "tdf: too many column tiles");
-    const float* bias = L.has_bias ? (const float*)L.bias.p : nullptr;
-    static const int yfast = env_int("ALSEP_TDF_YFAST", 1);
     const int nrb = L.M / Tc::BM;
-    const int nyb = (yfast && nrb > 1 && gx % 8 == 0 && gx * nrb <= 0x7fffffff) ? nrb : 0;
+    const int nyb = (switches().tdf_yfast && nrb > 1 && gx % 8 == 0 && gx * nrb <= 0x7fffffff) ? nrb : 0;
     const dim3 grid = nyb ? dim3((unsigned)(gx * nrb)) : dim3((unsigned)gx, nrb);
-    ProfScope prof(ctx, ALSEP_PROF_TDF);
-    static const int rpf = env_int("ALSEP_TDF_RPF", 2);
-    const bool fold = WM == 4 && R && rpf != 0 && fin && C == Tc::UC && tdf_final_mode();
-    if (WM == 4 && R && rpf != 0 && tdf_wide_mode() == 1 && L.M % TdfPersist::BM == 0 && (C == Tc::UC || C == 2 * Tc::UC) &&
-        (L.K == 384 || L.K == 192)) {
-        const int kind = fold ? kTdfPersistFinal : (L.K == 384 ? kTdfPersistK384 : kTdfPersistK192);
-        const int mode = tdf_persist_mode();
-        if (mode >= 2 || (mode == 1 && (kTdfPersistRouted & kind)))
-            return launch_tdf_persist(ctx, L, X, Y, R, nunits, C, fold ? fin : nullptr);
-    }
-    if (fold) {
-        ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)tdf_bf16_wide_kernel<4, true, 2, true>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)TdfWide<4>::lds_bytes));
-        hipLaunchKernelGGL((tdf_bf16_wide_kernel<4, true, 2, true>), grid, dim3(TdfWide<4>::THREADS), TdfWide<4>::lds_bytes,
-                           ctx->stream, X, Y, (const bf16_t*)L.wwide.p, bias, (const float*)L.scale.p, (const float*)L.shift.p, R,
-                           L.M, L.K, nunits, C, nyb, fin->w, fin->b, (bf16_t*)fin->out, fin->alpha);
-        fin->done = true;
-        note_launch(ctx, "tdf_bf16_wide_kernel<res,final>");
-    } else if (R && rpf == 0) {                                     // timing comparison only: residual rows loaded where they are used
-        ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)tdf_bf16_wide_kernel<WM, true, 0>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)Tc::lds_bytes));
-        hipLaunchKernelGGL((tdf_bf16_wide_kernel<WM, true, 0>), grid, dim3(Tc::THREADS), Tc::lds_bytes, ctx->stream, X, Y,
-                           (const bf16_t*)L.wwide.p, bias, (const float*)L.scale.p, (const float*)L.shift.p, R, L.M, L.K,
-                           nunits, C, nyb, (const float*)nullptr, (const float*)nullptr, (bf16_t*)nullptr, 0.f);
-    } else if (R) {
-        ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)tdf_bf16_wide_kernel<WM, true>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)Tc::lds_bytes));
-        hipLaunchKernelGGL((tdf_bf16_wide_kernel<WM, true>), grid, dim3(Tc::THREADS), Tc::lds_bytes, ctx->stream, X, Y,
-                           (const bf16_t*)L.wwide.p, bias, (const float*)L.scale.p, (const float*)L.shift.p, R, L.M, L.K,
-                           nunits, C, nyb, (const float*)nullptr, (const float*)nullptr, (bf16_t*)nullptr, 0.f);
-    } else {
-        ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)tdf_bf16_wide_kernel<WM, false>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)Tc::lds_bytes));
-        hipLaunchKernelGGL((tdf_bf16_wide_kernel<WM, false>), grid, dim3(Tc::THREADS), Tc::lds_bytes, ctx->stream, X, Y,
-                           (const bf16_t*)L.wwide.p, bias, (const float*)L.scale.p, (const float*)L.shift.p, R, L.M, L.K,
-                           nunits, C, nyb, (const float*)nullptr, (const float*)nullptr, (bf16_t*)nullptr, 0.f);
-    }
-    note_launch(ctx, R ? "tdf_bf16_wide_kernel<res>" : "tdf_bf16_wide_kernel<nores>");
-    ALSEP_LAUNCH_CHECK(ctx, "tdf_bf16_wide_kernel");
-    return ALSEP_OK;
+    ProfScope prof(ctx, r.prof_class);
+    const hipError_t e = launch(ctx, tdf_bf16_wide_kernel<WM, RES, RPF, FINAL>, grid, dim3(Tc::THREADS), Tc::lds_bytes, kLdsRaise, X, Y,
+                                (const bf16_t*)L.wwide.p, L.has_bias ? (const float*)L.bias.p : nullptr, (const float*)L.scale.p,
+                                (const float*)L.shift.p, R, L.M, L.K, nunits, C, nyb, fin ? fin->w : nullptr, fin ? fin->b : nullptr,
+                                fin ? (bf16_t*)fin->out : nullptr, fin ? fin->alpha : 0.f);
+    ALSEP_HIP(ctx, e);
+    if (fin) fin->done = true;
+    return finish_launch(ctx, r);
+}
+
+// route_tdf_dma has checked: R != nullptr, M % 384 == 0, K = 64 NT (384 or 192), C 48 or 96, nunits % 4 == 0; fin: FINAL only (C == 48)
+template <int NT, bool FINAL>
+int launch_tdf_persist(alsep_ctx* ctx, const TdfRoute& r, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* R, int64_t nunits, int C,
+                       FinalFold* fin) {
+    const int64_t nitems = nunits / TdfPersist::UN;
+    ProfScope prof(ctx, r.prof_class);
+    const hipError_t e = launch(ctx, tdf_bf16_persist_kernel<NT, FINAL>, dim3(per_cu_grid(ctx, switches().tdf_persist_grid, nitems)),   // 156.75 KiB of LDS
+                                dim3(TdfPersist::THREADS), TdfPersist::lds_bytes(NT, FINAL), kLdsRaise, X, Y, (const bf16_t*)L.wwide.p,
+                                L.has_bias ? (const float*)L.bias.p : nullptr, (const float*)L.scale.p, (const float*)L.shift.p, R, L.M, nitems, C,
+                                fin ? fin->w : nullptr, fin ? fin->b : nullptr, fin ? (bf16_t*)fin->out : nullptr, fin ? fin->alpha : 0.f);
+    ALSEP_HIP(ctx, e);
+    if (fin) fin->done = true;
+    return finish_launch(ctx, r);
 }
 
 int run_tdf_dma(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* R, const bf16_t* zp,
                 int64_t BT, int C, FinalFold* fin) {
-    typedef TdfB16 Tc;
-    const int64_t nunits = BT * (C / Tc::UC);
-    if (L.wwide.p && tdf_wide_mode() && L.K % 64 == 0 && nunits % 4 == 0) {
-        const int mode = tdf_wide_mode();
-        const bool can8 = L.M % 384 == 0;
-        const bool use8 = mode == 8 ? can8 : (mode == 4 ? false : (can8 && L.M == 384 && !R));
-        return use8 ? launch_tdf_wide<8>(ctx, L, X, Y, R, nunits, C, nullptr) : launch_tdf_wide<4>(ctx, L, X, Y, R, nunits, C, fin);
+    typedef TdfKernel K;
+    static_assert(TdfWide<4>::UN == TdfB16::UN && TdfWide<8>::UN == TdfB16::UN, "one column-tile count for every instance");
+    const int64_t nunits = BT * (C / TdfB16::UC);
+    if (ceil_div64(nunits, TdfB16::UN) > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "tdf: too many column tiles");
+    const TdfRoute r = route_tdf_dma(switches(), L, R != nullptr, fin != nullptr, nunits, C);
+    switch (r.kernel) {
+    case K::Plain: return launch_tdf_plain(ctx, r, L, X, Y, R, zp, nunits, C);
+    case K::Wide4Nores: return launch_tdf_wide<4, false, 2, false>(ctx, r, L, X, Y, R, nunits, C, nullptr);
+    case K::Wide4Res: return launch_tdf_wide<4, true, 2, false>(ctx, r, L, X, Y, R, nunits, C, nullptr);
+    case K::Wide4Rpf0: return launch_tdf_wide<4, true, 0, false>(ctx, r, L, X, Y, R, nunits, C, nullptr);
+    case K::Wide4Final: return launch_tdf_wide<4, true, 2, true>(ctx, r, L, X, Y, R, nunits, C, fin);
+    case K::Wide8Nores: return launch_tdf_wide<8, false, 2, false>(ctx, r, L, X, Y, R, nunits, C, nullptr);
+    case K::Wide8Res: return launch_tdf_wide<8, true, 2, false>(ctx, r, L, X, Y, R, nunits, C, nullptr);
+    case K::Wide8Rpf0: return launch_tdf_wide<8, true, 0, false>(ctx, r, L, X, Y, R, nunits, C, nullptr);
+    case K::Persist384: return launch_tdf_persist<6, false>(ctx, r, L, X, Y, R, nunits, C, nullptr);
+    case K::Persist192: return launch_tdf_persist<3, false>(ctx, r, L, X, Y, R, nunits, C, nullptr);
+    case K::Persist384Final: return launch_tdf_persist<6, true>(ctx, r, L, X, Y, R, nunits, C, fin);
+    case K::Persist192Final: return launch_tdf_persist<3, true>(ctx, r, L, X, Y, R, nunits, C, fin);
     }
-    const int64_t gx = ceil_div64(nunits, Tc::UN);
-    if (gx > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "tdf: too many column tiles");
-    const float* bias = L.has_bias ? (const float*)L.bias.p : nullptr;
-    ProfScope prof(ctx, ALSEP_PROF_TDF);
-    const dim3 grid((unsigned)gx, L.Mp / Tc::BM);
-    if (R)
-        hipLaunchKernelGGL((tdf_bf16_kernel<true>), grid, dim3(kThreads), Tc::lds_bytes, ctx->stream, X, Y, (const bf16_t*)L.w.p,
-                           bias, (const float*)L.scale.p, (const float*)L.shift.p, R, zp, L.M, L.K, L.Kp, nunits, C);
-    else
-        hipLaunchKernelGGL((tdf_bf16_kernel<false>), grid, dim3(kThreads), Tc::lds_bytes, ctx->stream, X, Y, (const bf16_t*)L.w.p,
-                           bias, (const float*)L.scale.p, (const float*)L.shift.p, R, zp, L.M, L.K, L.Kp, nunits, C);
-    ALSEP_LAUNCH_CHECK(ctx, "tdf_bf16_kernel");
-    return ALSEP_OK;
-}
-int run_tdf_dma(alsep_ctx* ctx, const GemmLayer&, const float*, float*, const float*, const float*, int64_t, int, FinalFold*) {
-    return alsep_fail(ctx, ALSEP_ERR_STATE, "LDS-DMA TDF path is bf16 only");
+    return alsep_fail(ctx, ALSEP_ERR_STATE, "tdf: no such route");
 }
 
 template <typename T>
 int run_tdf(alsep_ctx* ctx, const GemmLayer& L, const T* X, T* Y, const T* R, int64_t BT, int C, const void* zero_page,
             FinalFold* fin = nullptr) {
     typedef GemmCfg<T> Gc;
+    if constexpr (std::is_same<T, float>::value) {
 #ifndef ALSEP_F16_TU
-    if (L.split) return run_tdf_split(ctx, L, X, Y, R, BT, C);
+        if (L.split) return run_tdf_split(ctx, L, X, Y, R, BT, C);
 #endif
-    if (L.dma_path) return run_tdf_dma(ctx, L, X, Y, R, (const T*)zero_page, BT, C, fin);
+    } else {
+        if (L.dma_path) return run_tdf_dma(ctx, L, X, Y, R, (const T*)zero_page, BT, C, fin);
+    }
     const int64_t nunits = BT * (C / 16);
     const int64_t gx = ceil_div64(nunits, 8);
     if (gx > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "tdf_gemm: too many column tiles");
     const float* bias = L.has_bias ? (const float*)L.bias.p : nullptr;
     ProfScope prof(ctx, ALSEP_PROF_TDF);
-    if (R)
-        hipLaunchKernelGGL((tdf_gemm_kernel<T, true>), dim3((unsigned)gx, L.Mp / Gc::BR), dim3(kThreads), Gc::lds_bytes,
-                           ctx->stream, X, Y, (const T*)L.w.p, bias, (const float*)L.scale.p, (const float*)L.shift.p, R,
-                           L.M, L.K, L.Kp, nunits, C);
-    else
-        hipLaunchKernelGGL((tdf_gemm_kernel<T, false>), dim3((unsigned)gx, L.Mp / Gc::BR), dim3(kThreads), Gc::lds_bytes,
-                           ctx->stream, X, Y, (const T*)L.w.p, bias, (const float*)L.scale.p, (const float*)L.shift.p, R,
-                           L.M, L.K, L.Kp, nunits, C);
+    const hipError_t e = dispatch_bool(R != nullptr, [&](auto res) {
+        return launch(ctx, tdf_gemm_kernel<T, decltype(res)::value>, dim3((unsigned)gx, L.Mp / Gc::BR), dim3(kThreads), Gc::lds_bytes, kLdsAsIs,
+                      X, Y, (const T*)L.w.p, bias, (const float*)L.scale.p, (const float*)L.shift.p, R, L.M, L.K, L.Kp, nunits, C);
+    });
+    ALSEP_HIP(ctx, e);
     ALSEP_LAUNCH_CHECK(ctx, "tdf_gemm_kernel");
     return ALSEP_OK;
 }
 
-// ALSEP_TDF_FUSED: 1 (default) = the two TDF linears of a block run as one launch of tdf_bf16_fused_kernel at the levels in
-// kTdfFusedRouted (a level is routed there only where, in kernel traces of one session, the fused launch's mean and max lay below
-// the sum of the two old launches' minima: profiles/tdf_fused_kernel_stats.txt), and only at no fewer items than the level was
-// measured at (kTdfFusedFloor: the bench's 52 windows -- 9984 items at F = 768, 3328 at F = 384; below that the workgroups run
-// fewer rounds and nothing was measured); 0 = never (two launches of tdf_bf16_kernel, as before); 2 = every shape an instance
-// serves (bf16 / f16 on the DMA path, bn = 8, F = 768 or 384, C a multiple of 48 up to 192), without the floor (tests).
-// ALSEP_TDF_FUSED_GRID=n caps its grid (tests: several items per workgroup at small shapes).
-enum { kTdfFusedF768 = 1, kTdfFusedF384 = 2 };
-constexpr int kTdfFusedRouted = kTdfFusedF768 | kTdfFusedF384;
-constexpr int64_t kTdfFusedFloor[2] = {9984, 3328};
-int tdf_fused_mode() {
-    static const int v = env_int("ALSEP_TDF_FUSED", 1);
-    return v;
+// Both TDF linears of a block (A, then B with the residual) as one launch: None = the caller runs them one by one
+enum class TdfFusedKernel { None, F768, F384 };
+typedef Route<TdfFusedKernel> TdfFusedRoute;
+
+TdfFusedRoute route_tdf_fused(const Switches& s, const GemmLayer& A, const GemmLayer& B, int64_t BT, int C) {
+    typedef TdfFusedKernel K;
+    const TdfFusedRoute none = {K::None, ALSEP_PROF_TDF, nullptr, {}};
+    const int mode = s.tdf_fused;
+    if (mode <= 0 || !A.dma_path || !B.dma_path || !A.wfused.p || !B.wfused.p || C % 48 != 0 || C > TdfFused<768>::CMAX) return none;
+    const bool f768 = B.M == 768;
+    const int64_t nunits = BT * (C / 48);
+    const int nu = f768 ? TdfFused<768>::NU : TdfFused<384>::NU;
+    if (nunits <= 0 || nunits % nu != 0 || nunits > 0x7fffffff) return none;
+    const int64_t nitems = nunits / nu;
+    if (mode == 1 && (!(kTdfFusedRouted & (f768 ? kTdfFusedF768 : kTdfFusedF384)) || nitems < kTdfFusedFloor[f768 ? 0 : 1])) return none;
+    return {f768 ? K::F768 : K::F384, ALSEP_PROF_TDF, "tdf_bf16_fused_kernel", {"tdf_bf16_kernel", "tdf_bf16_kernel"}};   // two layer launches
 }
+
 template <int F_>
-int launch_tdf_fused(alsep_ctx* ctx, const GemmLayer& A, const GemmLayer& B, const bf16_t* X, bf16_t* Y, int64_t nitems, int C) {
+int launch_tdf_fused(alsep_ctx* ctx, const TdfFusedRoute& r, const GemmLayer& A, const GemmLayer& B, const bf16_t* X, bf16_t* Y, int64_t BT, int C) {
     typedef TdfFused<F_> P;
-    static const int cap = env_int("ALSEP_TDF_FUSED_GRID", 0);
-    int64_t grid = device_cu_count(ctx);                             // 156 / 159 KiB of LDS: one workgroup per CU
-    if (cap > 0 && cap < grid) grid = cap;
-    if (nitems < grid) grid = nitems;
-    ProfScope prof(ctx, ALSEP_PROF_TDF);
-    ALSEP_HIP(ctx, hipFuncSetAttribute((const void*)tdf_bf16_fused_kernel<F_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P::lds_bytes));
-    hipLaunchKernelGGL((tdf_bf16_fused_kernel<F_>), dim3((unsigned)grid), dim3(P::THREADS), P::lds_bytes, ctx->stream, X, Y,
-                       (const bf16_t*)A.wfused.p, (const bf16_t*)B.wfused.p, A.has_bias ? (const float*)A.bias.p : nullptr,
-                       (const float*)A.scale.p, (const float*)A.shift.p, B.has_bias ? (const float*)B.bias.p : nullptr,
-                       (const float*)B.scale.p, (const float*)B.shift.p, (int)nitems, C);
-    note_launch(ctx, "tdf_bf16_kernel");                             // the pinned name counts layer launches, whichever instance
-    note_launch(ctx, "tdf_bf16_kernel");                             // serves them: this launch is two of them
-    ALSEP_LAUNCH_CHECK(ctx, "tdf_bf16_fused_kernel");
-    return ALSEP_OK;
+    const int64_t nitems = BT * (C / 48) / P::NU;
+    ProfScope prof(ctx, r.prof_class);
+    const hipError_t e = launch(ctx, tdf_bf16_fused_kernel<F_>, dim3(per_cu_grid(ctx, switches().tdf_fused_grid, nitems)),   // 156 / 159 KiB of LDS
+                                dim3(P::THREADS), P::lds_bytes, kLdsRaise, X, Y, (const bf16_t*)A.wfused.p, (const bf16_t*)B.wfused.p,
+                                A.has_bias ? (const float*)A.bias.p : nullptr, (const float*)A.scale.p, (const float*)A.shift.p,
+                                B.has_bias ? (const float*)B.bias.p : nullptr, (const float*)B.scale.p, (const float*)B.shift.p, (int)nitems, C);
+    ALSEP_HIP(ctx, e);
+    return finish_launch(ctx, r);
 }
 // Both linears of blk as one launch where ALSEP_TDF_FUSED routes it (*done); otherwise nothing is launched and the caller runs them.
 int run_tdf_fused(alsep_ctx* ctx, const Block& blk, const bf16_t* X, bf16_t* Y, int64_t BT, int C, bool* done) {
     const GemmLayer& A = blk.tdf[0];
     const GemmLayer& B = blk.tdf[1];
-    const int mode = tdf_fused_mode();
-    if (mode <= 0 || !A.dma_path || !B.dma_path || !A.wfused.p || !B.wfused.p || C % 48 != 0 || C > TdfFused<768>::CMAX) return ALSEP_OK;
-    const bool f768 = B.M == 768;
-    const int64_t nunits = BT * (C / 48);
-    const int nu = f768 ? TdfFused<768>::NU : TdfFused<384>::NU;
-    if (nunits <= 0 || nunits % nu != 0 || nunits > 0x7fffffff) return ALSEP_OK;
-    const int64_t nitems = nunits / nu;
-    if (mode == 1 && (!(kTdfFusedRouted & (f768 ? kTdfFusedF768 : kTdfFusedF384)) || nitems < kTdfFusedFloor[f768 ? 0 : 1])) return ALSEP_OK;
-    *done = true;
-    return f768 ? launch_tdf_fused<768>(ctx, A, B, X, Y, nitems, C) : launch_tdf_fused<384>(ctx, A, B, X, Y, nitems, C);
+    const TdfFusedRoute r = route_tdf_fused(switches(), A, B, BT, C);
+    *done = r.kernel != TdfFusedKernel::None;
+    switch (r.kernel) {
+    case TdfFusedKernel::None: break;
+    case TdfFusedKernel::F768: return launch_tdf_fused<768>(ctx, r, A, B, X, Y, BT, C);
+    case TdfFusedKernel::F384: return launch_tdf_fused<384>(ctx, r, A, B, X, Y, BT, C);
+    }
+    return ALSEP_OK;
 }
-int run_tdf_fused(alsep_ctx*, const Block&, const float*, float*, int64_t, int, bool*) { return ALSEP_OK; }     // float32: never
 
 // TFC_TDF block: cur -> dest, using scratch a, b (cur may alias b), hidden h.  fin (last block of the network only): the
 // residual TDF launch may produce the network's output instead of dest (FinalFold).
@@ -3546,8 +3525,10 @@ int run_block(alsep_ctx* ctx, const alsep_net* net, const Block& blk, const T* c
         src = dst;
     }
     if (blk.tdf.size() == 2) {
-        bool fused = false;
-        if ((rc = run_tdf_fused(ctx, blk, src, dest, B * Th, c, &fused)) || fused) return rc;
+        if constexpr (!std::is_same<T, float>::value) {      // a float32 block has no fused image
+            bool fused = false;
+            if ((rc = run_tdf_fused(ctx, blk, src, dest, B * Th, c, &fused)) || fused) return rc;
+        }
         if ((rc = run_tdf<T>(ctx, blk.tdf[0], src, h, (const T*)nullptr, B * Th, c, net->zero_page.p))) return rc;
         return run_tdf<T>(ctx, blk.tdf[1], h, dest, src, B * Th, c, net->zero_page.p, fin);
     }
@@ -3610,9 +3591,8 @@ int forward_impl(alsep_ctx* ctx, const alsep_net* net, const T* in, T* out, int6
         ProfScope prof(ctx, ALSEP_PROF_POINTWISE);
         const int ppb = kFirstThreads / (cfg.g / Vec16<T>::N);
         const int64_t nblk = std::min<int64_t>(ceil_div64(npix0, ppb), 256 * 16);
-        hipLaunchKernelGGL((first_conv_kernel<T>), dim3((unsigned)nblk), dim3(kFirstThreads), 0,
-                           ctx->stream, in, P[0], (const float*)net->first_w.p, (const float*)net->first_scale.p,
-                           (const float*)net->first_shift.p, npix0, cfg.g, in_scale);
+        ALSEP_HIP(ctx, launch(ctx, first_conv_kernel<T>, dim3((unsigned)nblk), dim3(kFirstThreads), 0, kLdsAsIs, in, P[0], (const float*)net->first_w.p,
+                              (const float*)net->first_scale.p, (const float*)net->first_shift.p, npix0, cfg.g, in_scale));
         ALSEP_LAUNCH_CHECK(ctx, "first_conv_kernel");
     }
     // the last block may write `out` itself; the accumulating pass of a denoise pair (out_beta != 0) keeps the separate kernel
@@ -3647,9 +3627,8 @@ int forward_impl(alsep_ctx* ctx, const alsep_net* net, const T* in, T* out, int6
     }
     if (fold.done) return ALSEP_OK;
     ProfScope prof(ctx, ALSEP_PROF_POINTWISE);
-    hipLaunchKernelGGL((final_conv_kernel<T>), dim3((unsigned)ceil_div64(npix0, kThreads)), dim3(kThreads),
-                       (size_t)kThreads * cfg.g * sizeof(T), ctx->stream,
-                       (const T*)P[ic], out, (const float*)net->final_w.p, (const float*)net->final_b.p, npix0, cfg.g, out_alpha, out_beta);
+    ALSEP_HIP(ctx, launch(ctx, final_conv_kernel<T>, dim3((unsigned)ceil_div64(npix0, kThreads)), dim3(kThreads), (size_t)kThreads * cfg.g * sizeof(T),
+                          kLdsAsIs, (const T*)P[ic], out, (const float*)net->final_w.p, (const float*)net->final_b.p, npix0, cfg.g, out_alpha, out_beta));
     ALSEP_LAUNCH_CHECK(ctx, "final_conv_kernel");      // also counts the launch under that name
     return ALSEP_OK;
 }
