@@ -2982,6 +2982,14 @@ int finish_launch(alsep_ctx* ctx, const Route<K>& r) {
     ALSEP_LAUNCH_CHECK(ctx, r.check);
     return ALSEP_OK;
 }
+// The float32 launchers (exact and split) have no route: each counts one pinned name, whichever instance and grid order ran.  Beside it
+// they note alias names -- the conv instance ("conv3x3_f32s_kernel<24,48,32>", "conv3x3_kernel<f32,16,48,64>"), "<ny_fastest>" /
+// "<nrb_fast>" for the 1-D grid orders, "<res>" / "<nores>", "<ds>" / "<us>" -- so that a test asserts the branch it means to reach.
+void note_instance(alsep_ctx* ctx, const char* fmt, int a, int b, int c) {
+    char name[64];
+    snprintf(name, sizeof(name), fmt, a, b, c);
+    note_launch(ctx, name);
+}
 
 // ---- launches ------------------------------------------------------------------------------
 // One kernel launch on ctx->stream; kLdsRaise first raises the kernel's dynamic-LDS limit to `lds` (the launches above 64 KiB).
@@ -3023,6 +3031,7 @@ int launch_conv(alsep_ctx* ctx, const ConvLayer& L, const T* X, T* Y, int64_t B,
     conv_work(prof, L, sizeof(*X), B, Th, Fw);
     ALSEP_HIP(ctx, launch(ctx, conv3x3_kernel<T, KC, BN, TW>, dim3((unsigned)ntiles, L.cout / BN), dim3(kThreads), Cf::lds_bytes, kLdsRaise, X, Y,
                           (const T*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles));
+    if constexpr (std::is_same<T, float>::value) note_instance(ctx, "conv3x3_kernel<f32,%d,%d,%d>", KC, BN, TW);
     ALSEP_LAUNCH_CHECK(ctx, "conv3x3_kernel");
     return ALSEP_OK;
 }
@@ -3184,6 +3193,8 @@ int launch_conv_split(alsep_ctx* ctx, const ConvLayer& L, const float* X, float*
     const dim3 grid = nyf ? dim3((unsigned)(ntiles * nyc)) : dim3((unsigned)ntiles, nyc);
     ALSEP_HIP(ctx, launch(ctx, conv3x3_f32s_kernel<KC, BN, TW>, grid, dim3(kThreads), Cf::lds_bytes, kLdsRaise, X, Y, (const hs_t*)L.w.p,
                           (const float*)L.scale.p, (const float*)L.shift.p, Th, Fw, L.cin, L.cout, tiles_t, tiles_f, (int)ntiles, nyf, L.range_flag));
+    note_instance(ctx, "conv3x3_f32s_kernel<%d,%d,%d>", KC, BN, TW);
+    if (nyf) note_launch(ctx, "conv3x3_f32s_kernel<ny_fastest>");
     ALSEP_LAUNCH_CHECK(ctx, "conv3x3_f32s_kernel");
     return ALSEP_OK;
 }
@@ -3284,6 +3295,8 @@ int run_pix_split(alsep_ctx* ctx, const GemmLayer& L, const float* X, float* Y, 
     ALSEP_HIP(ctx, launch(ctx, pix_gemm_f32s_kernel<MODE>, fast ? dim3((unsigned)(gx * nrb)) : dim3((unsigned)gx, nrb), dim3(kThreads), Gc::lds_bytes,
                           kLdsRaise, X, Y, (const hs_t*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, skip, L.M, L.Mp, L.K, L.Kp, ncols,
                           Tp, Fp, C, C2, L.range_flag, fast));
+    note_launch(ctx, MODE == PIX_DS ? "pix_gemm_f32s_kernel<ds>" : "pix_gemm_f32s_kernel<us>");
+    if (fast) note_launch(ctx, "pix_gemm_f32s_kernel<nrb_fast>");
     ALSEP_LAUNCH_CHECK(ctx, "pix_gemm_f32s_kernel");
     return ALSEP_OK;
 }
@@ -3302,6 +3315,8 @@ int run_tdf_split(alsep_ctx* ctx, const GemmLayer& L, const float* X, float* Y, 
                       bias, (const float*)L.scale.p, (const float*)L.shift.p, R, L.M, L.Mp, L.K, L.Kp, nunits, C, L.range_flag, fast);
     });
     ALSEP_HIP(ctx, e);
+    note_launch(ctx, R ? "tdf_gemm_f32s_kernel<res>" : "tdf_gemm_f32s_kernel<nores>");
+    if (fast) note_launch(ctx, "tdf_gemm_f32s_kernel<nrb_fast>");
     ALSEP_LAUNCH_CHECK(ctx, "tdf_gemm_f32s_kernel");
     return ALSEP_OK;
 }
@@ -3322,6 +3337,7 @@ int run_pix(alsep_ctx* ctx, const GemmLayer& L, const T* X, T* Y, const T* skip,
     ProfScope prof(ctx, ALSEP_PROF_PIX);
     ALSEP_HIP(ctx, launch(ctx, pix_gemm_kernel<T, MODE>, dim3((unsigned)gx, L.Mp / Gc::BR), dim3(kThreads), Gc::lds_bytes, kLdsAsIs, X, Y,
                           (const T*)L.w.p, (const float*)L.scale.p, (const float*)L.shift.p, skip, L.M, L.K, L.Kp, ncols, Tp, Fp, C, C2));
+    if constexpr (std::is_same<T, float>::value) note_launch(ctx, MODE == PIX_DS ? "pix_gemm_kernel<f32,ds>" : "pix_gemm_kernel<f32,us>");
     ALSEP_LAUNCH_CHECK(ctx, "pix_gemm_kernel");
     return ALSEP_OK;
 }
@@ -3462,6 +3478,7 @@ int run_tdf(alsep_ctx* ctx, const GemmLayer& L, const T* X, T* Y, const T* R, in
                       X, Y, (const T*)L.w.p, bias, (const float*)L.scale.p, (const float*)L.shift.p, R, L.M, L.K, L.Kp, nunits, C);
     });
     ALSEP_HIP(ctx, e);
+    if constexpr (std::is_same<T, float>::value) note_launch(ctx, R ? "tdf_gemm_kernel<f32,res>" : "tdf_gemm_kernel<f32,nores>");
     ALSEP_LAUNCH_CHECK(ctx, "tdf_gemm_kernel");
     return ALSEP_OK;
 }
