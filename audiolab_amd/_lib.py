@@ -270,6 +270,12 @@ _SIGNATURES = {
     "alsep_nn_gru": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "alsep_rmvpe_sigmoid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "alsep_rmvpe_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
+    "alsep_nsf_source_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "alsep_nsf_source": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                   C.c_int64]),
+    "alsep_nsf_conv1d": (C.c_int, [C.c_void_p] * 7 + [C.c_int64] + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_float]),
+    "alsep_nsf_conv_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]),
+    "alsep_nsf_tconv1d": (C.c_int, [C.c_void_p] * 8 + [C.c_int64] + [C.c_int] * 5),
 }
 
 EXPORTS: Tuple[str, ...] = tuple(_SIGNATURES)

@@ -1668,3 +1668,4 @@ extern "C" int alsep_vr_band_spec(alsep_ctx* ctx, const float* spec_m, const flo
 
 #include "nn_hdemucs.h"
 #include "rmvpe.h"
+#include "nsf.h"

@@ -729,6 +729,33 @@ int alsep_rmvpe_sigmoid(alsep_ctx* ctx, float* x, int64_t n);
  * salience <= thred (compared in float32) and where f0 comes out as exactly 10 */
 int alsep_rmvpe_decode(alsep_ctx* ctx, const float* salience, int64_t T, float thred, double* f0);
 
+/* ---- RVC's NSF-HiFiGAN vocoder: replaces GeneratorNSF of modules/rvc/infer/lib/infer_pack/models.py (csrc/nsf.h).  Float32, the source's
+ * phase in float64; channels-last [L, C]; every pointer is a device pointer; pointers that carry channels are 16-byte aligned.  The
+ * contractions are exact f32 MFMA whatever alsep_nn_set_contraction says. ---- */
+/* bytes of workspace alsep_nsf_source needs for T frames; -1 when T < 1 or T > 2^20 */
+int64_t alsep_nsf_source_workspace_bytes(int64_t T);
+/* SourceModuleHnNSF with no overtones (models.py:313-446): f0 [T] (0 where unvoiced), noise [T upp] standard-normal draws ->
+ * har [T upp] = tanh(lin_w (0.1 sin(2 pi rad) uv + (uv ? 0.003 : 0.1 / 3) noise) + lin_b), uv = f0 > 0, rad = f0 / sr * j + acc[t] for
+ * sample j = 1 .. upp of frame t, acc[t] = fmod(sum over s < t of step[s], 1), step = fmod(f0 / sr * upp + 0.5, 1) - 0.5 in float32 as
+ * the reference computes it; the sum in float64, scanned in chunks of 1024 frames whatever the launch geometry.  upp 1 .. 1024. */
+int alsep_nsf_source(alsep_ctx* ctx, const float* f0, int64_t T, int upp, int sr, const float* noise, float lin_w, float lin_b, float* har,
+                     void* workspace, int64_t workspace_bytes);
+/* y [L, Cout] = out_scale (acc + post(conv1d(lrelu(x, pre_slope), w, dilation, padding dilation (K - 1) / 2) + bias + res)): one
+ * convolution of ResBlock1 (modules.py:223-236) with its residual, the running sum over the resblocks and their mean; conv_pre with
+ * pre_slope 1.  x [L, Cin]; w packed [K][Cin][Cout]; bias [Cout], res and acc [L, Cout] may each be NULL (y may be res or acc, not x);
+ * post 0 none, 1 tanh.  K odd 1 .. 11, dilation 1 .. 5, Cin and Cout multiples of 8 (16 for the unmasked kernels). */
+int alsep_nsf_conv1d(alsep_ctx* ctx, const float* x, const float* w, const float* bias, const float* res, const float* acc, float* y, int64_t L,
+                     int Cin, int Cout, int K, int dilation, float pre_slope, int post, float out_scale);
+/* y [L] = tanh(conv1d(lrelu(x, 0.01), w [7][C], padding 3)): conv_post (models.py:562-564); x [L, C], C a multiple of 8 */
+int alsep_nsf_conv_post(alsep_ctx* ctx, const float* x, const float* w, float* y, int64_t L, int C);
+/* one upsampling stage with its source injection (models.py:546-549): y [L u, Cout] = conv_transpose1d(lrelu(x, 0.1), w, stride u,
+ * padding (K - u) / 2) + bias + noise_conv(har); x [L, Cin]; w packed [K][Cin][Cout] from the module's [Cin][Cout][K]; har [L u s];
+ * noise_conv = Conv1d(1, Cout, 2 s, stride s, padding s / 2) for s > 1 and Conv1d(1, Cout, 1) for s = 1, noise_w packed [2 s or 1][Cout].
+ * ALSEP_ERR_ARG unless K - u is even and K >= u (otherwise the output is not L u long), K <= 8 u (the kernel walks at most 8 taps per
+ * output phase), s is 1 or even (an odd stride's noise convolution is one sample short), Cin and Cout are multiples of 8. */
+int alsep_nsf_tconv1d(alsep_ctx* ctx, const float* x, const float* w, const float* bias, const float* har, const float* noise_w,
+                      const float* noise_b, float* y, int64_t L, int Cin, int Cout, int K, int u, int s);
+
 #ifdef __cplusplus
 }
 #endif
