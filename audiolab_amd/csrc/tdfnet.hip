@@ -1285,8 +1285,18 @@ tdf_bf16_wide_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const
 //     latency sits under that row block's MFMAs (acc 2 x 3 x 3 = 72 VGPRs leaves room for the 40 they take);
 //   * BN scale / shift of the two units (the same for every item: C / 48 is 1 or 2) are read from LDS, not from memory;
 //   * FINAL: as in the wide kernel; the rounded rows reuse the wave's fp32 staging rows (read whole, then overwritten).
+//   * USF (NT = 3, C = 96): the 2x2 stride-2 transposed conv 96 -> 48 that follows the block, times the level-0 skip, is
+//     computed here and Y is never written.  An item is one frame (both 48-channel halves), so after the epilogue above a wave
+//     holds 48 whole level-1 pixels, rounded once to the storage type as the store would have: unit 0's stay in registers
+//     while unit 1 goes through the staging rows, then both take the staging rows' place as [48 px][96 c] and become the B
+//     fragments (9 x 16 bytes per lane).  The us weights (A operand, 36 KiB in fragment order, in LDS once per workgroup) meet
+//     them in chunks of one output row dy x 16 input pixels = 32 output pixels x 48 channels: one accumulator per (tap, m-tile,
+//     16-pixel block) over ks = 0, 1, 2 -- us_stream_kernel<96, 48>'s chains -- then relu(bn(.)) in fp32 through the staging
+//     rows, times the skip in fp32, one rounding, whole 3 KiB runs of 16-byte stores (the 48 rows are 9216 contiguous bytes
+//     of frame 2t and of frame 2t + 1).  The skip runs are requested kUsfAhead chunks ahead, the first ones behind unit 0's
+//     TDF epilogue.  No LDS-DMA is in flight in a row block, so these compiler-tracked loads get counted waits.
 // LDS: 72 KiB tile + 8 x 9.75 KiB staging + 0.75 KiB scale/shift (+ 6 KiB final weights) = 156.75 KiB: one workgroup of
-// eight waves per CU, two waves per SIMD.
+// eight waves per CU, two waves per SIMD.  USF: 36 + 78 + 0.75 + 36.4 = 151.1 KiB.
 // ------------------------------------------------------------------------------------------
 struct TdfPersist {
     static constexpr int WV = 8, TR = 48, BM = TR * WV, UN = 2, UC = 48, BK = 64;
@@ -1296,8 +1306,28 @@ struct TdfPersist {
     static constexpr size_t stage_bytes = (size_t)WV * TR * SS * sizeof(float);
     static constexpr size_t bn_bytes = (size_t)UN * 2 * UC * sizeof(float);
     static constexpr size_t tile_bytes(int nt) { return (size_t)nt * STAGE_ELEMS * sizeof(bf16_t); }
-    static constexpr size_t lds_bytes(int nt, bool fin) { return tile_bytes(nt) + stage_bytes + bn_bytes + (fin ? WV * FWN * sizeof(float) : 0); }
+    // USF (C = 96 -> 48 upsampling folded in): XS = row stride of the wave's rounded pixels [48 f'][96 c] bf16, which take the
+    // place of its fp32 staging rows; the us layer's fragment-order weights [4 taps][3 m-tiles][3 k-steps][64 lanes][8] and its
+    // scale | shift lie behind the TDF scale / shift
+    static constexpr int XS = 104, USC = 96, USC2 = 48, US_MT = 3, US_KS = 3, US_NB = TR / 16;
+    static constexpr size_t usw_bytes = (size_t)4 * US_MT * US_KS * 64 * 8 * sizeof(bf16_t);
+    static constexpr size_t usf_bytes = usw_bytes + 2 * USC2 * sizeof(float);
+    static constexpr size_t lds_bytes(int nt, bool fin, bool usf = false) {
+        return tile_bytes(nt) + stage_bytes + bn_bytes + (fin ? WV * FWN * sizeof(float) : 0) + (usf ? usf_bytes : 0);
+    }
     static_assert((size_t)TR * FS * sizeof(bf16_t) <= (size_t)TR * SS * sizeof(float), "FINAL: the rounded rows fit in the staging rows");
+    static_assert((size_t)TR * XS * sizeof(bf16_t) <= (size_t)TR * SS * sizeof(float) && XS >= USC && XS % 8 == 0,
+                  "USF: the rounded pixels fit in the staging rows, 16-byte aligned");
+    static_assert((size_t)32 * SS * sizeof(float) <= (size_t)TR * SS * sizeof(float), "USF: 32 output pixels of a chunk in the staging rows");
+};
+// The 96 -> 48 upsampling that follows a level-1 block, folded into tdf_bf16_persist_kernel<3, false, true>: the us layer's
+// fragment-order weights, BN scale / shift, the level-0 skip it multiplies by and the level-0 activation it writes.
+struct UsFoldArgs {
+    const bf16_t* w;
+    const float* scale;
+    const float* shift;
+    const bf16_t* skip;
+    bf16_t* out;
 };
 
 // glds16 with the source as wave-uniform global base + 32-bit lane offset (one address VGPR, no 64-bit lane pointer)
@@ -1305,15 +1335,19 @@ __device__ __forceinline__ void glds16_base(const ALSEP_GLOBAL char* gbase, unsi
     __builtin_amdgcn_global_load_lds((const ALSEP_GLOBAL void*)(gbase + lane_off), (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
-template <int NT, bool FINAL>
+constexpr int kUsfAhead = 3;                                         // USF: skip runs requested this many chunks ahead (12 VGPRs each)
+
+template <int NT, bool FINAL, bool USF = false>
 __global__ void __launch_bounds__(TdfPersist::THREADS, 1)
 tdf_bf16_persist_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, const bf16_t* __restrict__ Wf,
                         const float* __restrict__ bias, const float* __restrict__ scale, const float* __restrict__ shift,
                         const bf16_t* __restrict__ R, int M, int64_t nitems, int C,
-                        const float* __restrict__ FW, const float* __restrict__ FB, bf16_t* __restrict__ FOUT, float falpha) {
+                        const float* __restrict__ FW, const float* __restrict__ FB, bf16_t* __restrict__ FOUT, float falpha,
+                        UsFoldArgs UF) {
     typedef TdfPersist Tc;
     static_assert(NT % 3 == 0 && NT >= 3, "three weight buffers: a K tile's buffer is the same in every row block");
-    static_assert(Tc::lds_bytes(NT, FINAL) <= 160 * 1024, "LDS of a CU");
+    static_assert(Tc::lds_bytes(NT, FINAL, USF) <= 160 * 1024, "LDS of a CU");
+    static_assert(!USF || (NT == 3 && !FINAL), "USF: the level-1 residual linear (K = 192), launched with C = 96");
     constexpr int K = NT * Tc::BK;
     bf16_t* tile = reinterpret_cast<bf16_t*>(alsep_smem);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1330,6 +1364,14 @@ tdf_bf16_persist_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, co
     if (tid < Tc::UN * 2 * Tc::UC) {
         const int u = tid / (2 * Tc::UC), which = (tid / Tc::UC) & 1, c = tid % Tc::UC;
         bnl[tid] = (which ? shift : scale)[(u & ush) * Tc::UC + c];
+    }
+    // USF only: behind the TDF scale / shift; both are complete behind the first item's barrier
+    bf16_t* usw = reinterpret_cast<bf16_t*>(alsep_smem + Tc::tile_bytes(NT) + Tc::stage_bytes + Tc::bn_bytes);
+    float* usbn = reinterpret_cast<float*>(alsep_smem + Tc::tile_bytes(NT) + Tc::stage_bytes + Tc::bn_bytes + Tc::usw_bytes);   // [scale | shift][48]
+    if constexpr (USF) {
+        for (int i = tid; i < (int)(Tc::usw_bytes / 16); i += Tc::THREADS)
+            *reinterpret_cast<bf16x8*>(usw + (size_t)i * 8) = *reinterpret_cast<const bf16x8*>(UF.w + (size_t)i * 8);
+        if (tid < 2 * Tc::USC2) usbn[tid] = (tid < Tc::USC2 ? UF.scale : UF.shift)[tid % Tc::USC2];
     }
     float fbs[4];
     if (FINAL) {
@@ -1450,9 +1492,23 @@ tdf_bf16_persist_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, co
 
             // Epilogue of this wave's 48 rows, one unit at a time through its private staging rows: arithmetic exactly as in
             // tdf_bf16_wide_kernel (bias, BN, ReLU and the residual add in fp32, one rounding).
+            // USF: chunk ch = dy * 3 + nb is output row 2 t + dy, output pixels 2 (48 rowblk + 16 nb) + [0, 32): 3 KiB, contiguous
+            // in the skip and in the output alike; lane l moves bytes [16 l, 16 l + 16) of each of its three KiB
+            constexpr int USF_CHUNKS = 2 * Tc::US_NB;
+            auto usf_chunk_off = [&](int ch) {
+                return ((2 * (u0 >> 1) + ch / Tc::US_NB) * (2 * (int64_t)M) + 2 * (rowblk * Tc::TR + (ch % Tc::US_NB) * 16)) * Tc::USC2;
+            };
+            bf16x8 skv[USF ? USF_CHUNKS : 1][3];
+            auto usf_load_skip = [&](int ch) {
+                const ALSEP_GLOBAL char* sp = opaque_uniform_gptr(reinterpret_cast<const char*>(UF.skip + usf_chunk_off(ch)));
+#pragma unroll
+                for (int g = 0; g < 3; ++g) skv[ch][g] = *reinterpret_cast<const ALSEP_GLOBAL bf16x8*>(sp + woff + g * 1024);
+            };
+            bf16x8 qq[Tc::UN][5];                                    // USF: both units' rounded rows
 #pragma unroll
             for (int u = 0; u < Tc::UN; ++u) {
-                ALSEP_GLOBAL char* yb = const_cast<ALSEP_GLOBAL char*>(opaque_uniform_gptr(reinterpret_cast<const char*>(Y + unit_base(u))));
+                ALSEP_GLOBAL char* yb = const_cast<ALSEP_GLOBAL char*>(                    // USF: Y is null and never written
+                    opaque_uniform_gptr(reinterpret_cast<const char*>(USF ? (const bf16_t*)nullptr : Y + unit_base(u))));
 #pragma unroll
                 for (int ni = 0; ni < 3; ++ni) {
                     const f32x4 sc = *reinterpret_cast<const f32x4*>(bnl + u * 2 * Tc::UC + ni * 16 + 4 * lq);
@@ -1479,10 +1535,18 @@ tdf_bf16_persist_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, co
                         for (int e = 0; e < 8; ++e) y[e] += (float)rr[u][g][e];
 #pragma unroll
                         for (int e = 0; e < 8; ++e) q[g][e] = (bf16_t)y[e];
-                        if (!FINAL) stream_store(reinterpret_cast<ALSEP_GLOBAL bf16x8*>(yb + loff[g]), q[g]);
+                        if (!FINAL && !USF) stream_store(reinterpret_cast<ALSEP_GLOBAL bf16x8*>(yb + loff[g]), q[g]);
+                        if (USF) qq[u][g] = q[g];
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
+                if constexpr (USF) {
+                    // the first skip runs, under unit 1's epilogue (unit 0's accumulators and residual rows are dead: room for them)
+                    if (u == 0) {
+#pragma unroll
+                        for (int ch = 0; ch < kUsfAhead && ch < USF_CHUNKS; ++ch) usf_load_skip(ch);
+                    }
+                }
                 if (FINAL) {
                     // every staging row is read: the rounded rows [48 f'][48 c] (row stride FS) take their place, then the chains
                     // of final_conv_kernel as in the wide kernel -- lane = f' row = one pixel of frame u0 + u (C == 48)
@@ -1517,6 +1581,77 @@ tdf_bf16_persist_kernel(const bf16_t* __restrict__ X, bf16_t* __restrict__ Y, co
                     for (int r = 0; r < 4; ++r) yq[r] = (bf16_t)y[r];
                     if (ln < Tc::TR) *reinterpret_cast<ALSEP_GLOBAL bf16x4*>(fo + (unsigned)ln * (4u * (unsigned)sizeof(bf16_t))) = yq;
                     __builtin_amdgcn_wave_barrier();                 // the next unit's staging rows overwrite these
+                }
+            }
+            if constexpr (USF) {
+                // every staging row is read: the wave's 48 rounded pixels [48 f'][96 c] take their place (unit u = channels 48 u ..)
+                // lane coordinates recomputed here, not kept (or spilled) across the k loop
+                const int ln = opaque_vgpr(lane), ul15 = ln & 15, ulq = ln >> 4;
+                bf16_t* xr = reinterpret_cast<bf16_t*>(stg);
+#pragma unroll
+                for (int u = 0; u < Tc::UN; ++u)
+#pragma unroll
+                    for (int g = 0; g < 5; ++g) {
+                        const int gidx = g * 64 + ln;
+                        if (gidx < Tc::TR * 6) *reinterpret_cast<bf16x8*>(xr + (gidx / 6) * Tc::XS + u * Tc::UC + (gidx % 6) * 8) = qq[u][g];
+                    }
+                __builtin_amdgcn_wave_barrier();
+                bf16x8 xb[Tc::US_NB][Tc::US_KS];                     // B fragments: pixel 16 nb + l15, channels 32 ks + 8 lq ..
+#pragma unroll
+                for (int nb = 0; nb < Tc::US_NB; ++nb)
+#pragma unroll
+                    for (int ks = 0; ks < Tc::US_KS; ++ks)
+                        xb[nb][ks] = *reinterpret_cast<const bf16x8*>(xr + (nb * 16 + ul15) * Tc::XS + ks * 32 + ulq * 8);
+                __builtin_amdgcn_wave_barrier();                     // the chunks' fp32 rows overwrite these
+#pragma unroll
+                for (int ch = 0; ch < USF_CHUNKS; ++ch) {
+                    const int dy = ch / Tc::US_NB, nb = ch % Tc::US_NB;
+                    if (ch + kUsfAhead < USF_CHUNKS) usf_load_skip(ch + kUsfAhead);
+                    f32x4 ua[2][Tc::US_MT];
+#pragma unroll
+                    for (int dx = 0; dx < 2; ++dx)
+#pragma unroll
+                        for (int mt = 0; mt < Tc::US_MT; ++mt) ua[dx][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    // six independent chains side by side, each over ks ascending (us_stream_kernel: tap = wave, wf[mt][ks])
+#pragma unroll
+                    for (int ks = 0; ks < Tc::US_KS; ++ks)
+#pragma unroll
+                        for (int dx = 0; dx < 2; ++dx)
+#pragma unroll
+                            for (int mt = 0; mt < Tc::US_MT; ++mt) {
+                                const bf16x8 wa = *reinterpret_cast<const bf16x8*>(
+                                    usw + ((size_t)(((dy * 2 + dx) * Tc::US_MT + mt) * Tc::US_KS + ks) * 64 + ln) * 8);
+                                mma_step(ua[dx][mt], wa, xb[nb][ks]);
+                            }
+                    // relu(bn(.)) in fp32 at output pixel 2 j + dx of the chunk's 32
+#pragma unroll
+                    for (int mt = 0; mt < Tc::US_MT; ++mt) {
+                        const f32x4 sc = *reinterpret_cast<const f32x4*>(usbn + mt * 16 + 4 * ulq);
+                        const f32x4 sh = *reinterpret_cast<const f32x4*>(usbn + Tc::USC2 + mt * 16 + 4 * ulq);
+#pragma unroll
+                        for (int dx = 0; dx < 2; ++dx) {
+                            f32x4 y;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) y[r] = fmaxf(fmaf(ua[dx][mt][r], sc[r], sh[r]), 0.f);
+                            *reinterpret_cast<f32x4*>(stg + (2 * l15 + dx) * Tc::SS + mt * 16 + 4 * ulq) = y;
+                        }
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    ALSEP_GLOBAL char* ob = const_cast<ALSEP_GLOBAL char*>(
+                        opaque_uniform_gptr(reinterpret_cast<const char*>(UF.out + usf_chunk_off(ch))));
+#pragma unroll
+                    for (int g = 0; g < 3; ++g) {                    // 32 pixels x 6 groups of 8 channels = 3 per lane
+                        const int gidx = g * 64 + ln;
+                        const float* src = stg + (gidx / 6) * Tc::SS + (gidx % 6) * 8;
+                        const f32x4 lo = *reinterpret_cast<const f32x4*>(src);
+                        const f32x4 hi = *reinterpret_cast<const f32x4*>(src + 4);
+                        const bf16x8 sk = skv[ch][g];
+                        bf16x8 q;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { q[e] = (bf16_t)(lo[e] * (float)sk[e]); q[4 + e] = (bf16_t)(hi[e] * (float)sk[4 + e]); }
+                        stream_store(reinterpret_cast<ALSEP_GLOBAL bf16x8*>(ob + (unsigned)ln * 16u + g * 1024), q);
+                    }
+                    __builtin_amdgcn_wave_barrier();                 // the next chunk's rows overwrite these
                 }
             }
         }
@@ -2905,6 +3040,10 @@ int build_net(alsep_net* net, const TensorMap& tm) {
 //                     in kTdfPersistRouted (each kind is routed there only where it measured faster than the wide kernel on the same box:
 //                     profiles/tdf_persist_kernel_stats.txt); 0 = never (the wide kernel, as before); 2 = every kind the kernel serves
 //                     (measurements, tests).  ALSEP_TDF_PERSIST_GRID=n caps its grid (tests: several items per workgroup at small shapes).
+//   ALSEP_TDF_US_FOLD 1 = the 96 -> 48 upsampling between levels 1 and 0 is folded into the residual TDF launch of the block
+//                     under it (tdf_bf16_persist_kernel<3, false, true>: the block's output never reaches memory) where that launch goes to
+//                     the persistent kernel at C = 96, K = 192 and the upsampling would run on us_stream_kernel<96, 48>; 0 = two
+//                     launches, as before.  Same bits either way.  ALSEP_TDF_PERSIST_GRID caps this launch's grid too.
 //   ALSEP_TDF_FUSED   1 (default) = the two TDF linears of a block run as one launch of tdf_bf16_fused_kernel at the levels in
 //                     kTdfFusedRouted (a level is routed there only where, in kernel traces of one session, the fused launch's mean and max lay below
 //                     the sum of the two old launches' minima: profiles/tdf_fused_kernel_stats.txt), and only at no fewer items than the level was
@@ -2915,7 +3054,7 @@ int build_net(alsep_net* net, const TensorMap& tm) {
 struct Switches {
     int conv_m0, conv_regw, conv_big, conv_mq, conv_big3, conv_allco, conv_allco_tw, conv_allco_grid, conv_nyfast;
     int pix_stream, pix_pipe, pix_pipe_grid;
-    int tdf_wide, tdf_yfast, tdf_rpf, tdf_final, tdf_persist, tdf_persist_grid, tdf_fused, tdf_fused_grid;
+    int tdf_wide, tdf_yfast, tdf_rpf, tdf_final, tdf_persist, tdf_persist_grid, tdf_us_fold, tdf_fused, tdf_fused_grid;
 };
 // Levels that measured faster on conv3x3_bf16_allco_kernel than on their kernel, same box, bench shape (profiles/conv_allco_kernel_stats.txt,
 // conv_allco_ab.txt; c = 192: conv_allco_groups_kernel_stats.txt, conv_allco_groups_ab.txt); only these are routed there by default.
@@ -2930,6 +3069,8 @@ constexpr int kTdfPersistRouted = kTdfPersistK384 | kTdfPersistK192 | kTdfPersis
 enum { kTdfFusedF768 = 1, kTdfFusedF384 = 2 };
 constexpr int kTdfFusedRouted = kTdfFusedF768 | kTdfFusedF384;
 constexpr int64_t kTdfFusedFloor[2] = {9984, 3328};
+// ALSEP_TDF_US_FOLD where it is not set (profiles/tdf_us_fold_kernel_stats.txt, tdf_us_fold_ab.txt)
+constexpr int kTdfUsFold = 1;
 
 const Switches& switches() {
     static const Switches s = [] {
@@ -2952,6 +3093,7 @@ const Switches& switches() {
         v.tdf_final = env_int("ALSEP_TDF_FINAL", 1);
         v.tdf_persist = env_int("ALSEP_TDF_PERSIST", 1);
         v.tdf_persist_grid = env_int("ALSEP_TDF_PERSIST_GRID", 0);
+        v.tdf_us_fold = env_int("ALSEP_TDF_US_FOLD", kTdfUsFold);
         v.tdf_fused = env_int("ALSEP_TDF_FUSED", 1);
         v.tdf_fused_grid = env_int("ALSEP_TDF_FUSED_GRID", 0);
         return v;
@@ -2966,14 +3108,14 @@ bool mask_routed(int mode, int routed, int kind) { return mode >= 2 || (mode == 
 // the names the launch is counted under -- `check`, which ALSEP_LAUNCH_CHECK reports and counts, and `also`.  The pinned launch names
 // (bench.py and the tests read them) count LAYER launches, whichever instance serves them: `also` holds the instance's own name where it
 // has one and the pinned names of the kernel it replaces -- an all-channels conv counts under big<3>'s or the plain kernel's names, a
-// persistent TDF launch under the wide kernel's, a fused TDF launch twice under tdf_bf16_kernel (it is two layers).  finish_launch() is
-// the only place that notes them.  A route function launches nothing and touches no ctx.
+// persistent TDF launch under the wide kernel's, a fused TDF launch twice under tdf_bf16_kernel (it is two layers), a residual TDF launch
+// with the upsampling folded in also under the us layer's names (it is that layer too).  finish_launch() is the only place that notes them.  A route function launches nothing and touches no ctx.
 template <typename K>
 struct Route {
     K kernel;
     int prof_class;
     const char* check;
-    const char* also[3];
+    const char* also[5];
 };
 template <typename K>
 int finish_launch(alsep_ctx* ctx, const Route<K>& r) {
@@ -3352,15 +3494,30 @@ struct FinalFold {
     float alpha;
     bool done;
 };
+// The 96 -> 48 upsampling between levels 1 and 0, offered in the same way to the last TDF launch of the block whose output it reads
+// (forward_impl offers it only where run_pix would launch us_stream_kernel<96, 48>): tdf_bf16_persist_kernel<3, false, true> writes
+// relu(bn(convT(block output))) * skip to `out` -- [2 BT][2 Fp][48], the block's own output buffer, which the launch never reads --
+// instead of the block's output, sets `done`, and forward_impl() then skips the us launch and takes `out` as its result.
+struct UsFold {
+    const GemmLayer* us;
+    const void* skip;
+    void* out;
+    int64_t BT;                                                // level-1 frames B Tp, each of Fp pixels x 96 channels
+    int Fp;
+    bool done;
+};
 
 // The instances that serve one TDF linear of a bf16 / f16 network with c % 48 == 0 (L.dma_path).  Wide<WM>: Nores = no residual,
-// Res = residual rows requested ahead, Rpf0 = residual rows loaded where they are used, Final = Res with the final 1x1 conv folded in.
+// Res = residual rows requested ahead, Rpf0 = residual rows loaded where they are used, Final = Res with the final 1x1 conv folded in,
+// Persist192Us = Persist192 with the 96 -> 48 upsampling folded in.
 enum class TdfKernel { Plain, Wide4Nores, Wide4Res, Wide4Rpf0, Wide4Final, Wide8Nores, Wide8Res, Wide8Rpf0,
-                       Persist384, Persist192, Persist384Final, Persist192Final };
+                       Persist384, Persist192, Persist384Final, Persist192Final, Persist192Us };
 typedef Route<TdfKernel> TdfRoute;
 
-// residual: the launch adds R; final_offered: the caller offers the final 1x1 conv (FinalFold); nunits = B T (C / 48)
-TdfRoute route_tdf_dma(const Switches& s, const GemmLayer& L, bool residual, bool final_offered, int64_t nunits, int C) {
+// residual: the launch adds R; final_offered: the caller offers the final 1x1 conv (FinalFold); us_offered: the caller offers the
+// 96 -> 48 upsampling (UsFold); nunits = B T (C / 48)
+TdfRoute route_tdf_dma(const Switches& s, const GemmLayer& L, bool residual, bool final_offered, int64_t nunits, int C,
+                       bool us_offered = false) {
     typedef TdfKernel K;
     typedef TdfWide<4> W4;
     const int cls = ALSEP_PROF_TDF;
@@ -3378,6 +3535,9 @@ TdfRoute route_tdf_dma(const Switches& s, const GemmLayer& L, bool residual, boo
         const int kind = fold ? kTdfPersistFinal : (L.K == 384 ? kTdfPersistK384 : kTdfPersistK192);
         if (mask_routed(s.tdf_persist, kTdfPersistRouted, kind)) {
             if (fold) return {L.K == 384 ? K::Persist384Final : K::Persist192Final, cls, persist, {res, "tdf_bf16_wide_kernel<res,final>"}};
+            // two layer launches in one: its own name, and the pinned names of the us layer it serves (route_pix_stream's Us96 row)
+            if (us_offered && s.tdf_us_fold && C == 2 * W4::UC && L.K == 192)
+                return {K::Persist192Us, cls, persist, {res, "tdf_bf16_persist_kernel<us>", "us_stream_kernel", "us_stream_kernel<96,48>", "pix stream kernel"}};
             return {L.K == 384 ? K::Persist384 : K::Persist192, cls, persist, {res}};
         }
     }
@@ -3427,19 +3587,39 @@ int launch_tdf_persist(alsep_ctx* ctx, const TdfRoute& r, const GemmLayer& L, co
     const hipError_t e = launch(ctx, tdf_bf16_persist_kernel<NT, FINAL>, dim3(per_cu_grid(ctx, switches().tdf_persist_grid, nitems)),   // 156.75 KiB of LDS
                                 dim3(TdfPersist::THREADS), TdfPersist::lds_bytes(NT, FINAL), kLdsRaise, X, Y, (const bf16_t*)L.wwide.p,
                                 L.has_bias ? (const float*)L.bias.p : nullptr, (const float*)L.scale.p, (const float*)L.shift.p, R, L.M, nitems, C,
-                                fin ? fin->w : nullptr, fin ? fin->b : nullptr, fin ? (bf16_t*)fin->out : nullptr, fin ? fin->alpha : 0.f);
+                                fin ? fin->w : nullptr, fin ? fin->b : nullptr, fin ? (bf16_t*)fin->out : nullptr, fin ? fin->alpha : 0.f,
+                                UsFoldArgs{});
     ALSEP_HIP(ctx, e);
     if (fin) fin->done = true;
     return finish_launch(ctx, r);
 }
 
+// route_tdf_dma has checked as for launch_tdf_persist, and C == 96, K == 192; forward_impl that usf->us is the 96 -> 48 layer with its
+// fragment-order image and that usf->out is neither X nor R.  The block's output is not written: Y is not passed on.
+int launch_tdf_persist_us(alsep_ctx* ctx, const TdfRoute& r, const GemmLayer& L, const bf16_t* X, const bf16_t* R, int64_t nunits, int C,
+                          UsFold* usf) {
+    const int64_t nitems = nunits / TdfPersist::UN;
+    if (usf->Fp != L.M || usf->BT != nitems || usf->out == (const void*)X || usf->out == (const void*)R)
+        return alsep_fail(ctx, ALSEP_ERR_STATE, "tdf: the offered upsampling does not fit the launch");
+    const UsFoldArgs ua = {(const bf16_t*)usf->us->wfrag.p, (const float*)usf->us->scale.p, (const float*)usf->us->shift.p,
+                           (const bf16_t*)usf->skip, (bf16_t*)usf->out};
+    ProfScope prof(ctx, r.prof_class);
+    const hipError_t e = launch(ctx, tdf_bf16_persist_kernel<3, false, true>, dim3(per_cu_grid(ctx, switches().tdf_persist_grid, nitems)),   // 151.1 KiB of LDS
+                                dim3(TdfPersist::THREADS), TdfPersist::lds_bytes(3, false, true), kLdsRaise, X, (bf16_t*)nullptr, (const bf16_t*)L.wwide.p,
+                                L.has_bias ? (const float*)L.bias.p : nullptr, (const float*)L.scale.p, (const float*)L.shift.p, R, L.M, nitems, C,
+                                (const float*)nullptr, (const float*)nullptr, (bf16_t*)nullptr, 0.f, ua);
+    ALSEP_HIP(ctx, e);
+    usf->done = true;
+    return finish_launch(ctx, r);
+}
+
 int run_tdf_dma(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t* Y, const bf16_t* R, const bf16_t* zp,
-                int64_t BT, int C, FinalFold* fin) {
+                int64_t BT, int C, FinalFold* fin, UsFold* usf) {
     typedef TdfKernel K;
     static_assert(TdfWide<4>::UN == TdfB16::UN && TdfWide<8>::UN == TdfB16::UN, "one column-tile count for every instance");
     const int64_t nunits = BT * (C / TdfB16::UC);
     if (ceil_div64(nunits, TdfB16::UN) > 0x7fffffff) return alsep_fail(ctx, ALSEP_ERR_ARG, "tdf: too many column tiles");
-    const TdfRoute r = route_tdf_dma(switches(), L, R != nullptr, fin != nullptr, nunits, C);
+    const TdfRoute r = route_tdf_dma(switches(), L, R != nullptr, fin != nullptr, nunits, C, usf != nullptr);
     switch (r.kernel) {
     case K::Plain: return launch_tdf_plain(ctx, r, L, X, Y, R, zp, nunits, C);
     case K::Wide4Nores: return launch_tdf_wide<4, false, 2, false>(ctx, r, L, X, Y, R, nunits, C, nullptr);
@@ -3453,20 +3633,21 @@ int run_tdf_dma(alsep_ctx* ctx, const GemmLayer& L, const bf16_t* X, bf16_t* Y, 
     case K::Persist192: return launch_tdf_persist<3, false>(ctx, r, L, X, Y, R, nunits, C, nullptr);
     case K::Persist384Final: return launch_tdf_persist<6, true>(ctx, r, L, X, Y, R, nunits, C, fin);
     case K::Persist192Final: return launch_tdf_persist<3, true>(ctx, r, L, X, Y, R, nunits, C, fin);
+    case K::Persist192Us: return launch_tdf_persist_us(ctx, r, L, X, R, nunits, C, usf);
     }
     return alsep_fail(ctx, ALSEP_ERR_STATE, "tdf: no such route");
 }
 
 template <typename T>
 int run_tdf(alsep_ctx* ctx, const GemmLayer& L, const T* X, T* Y, const T* R, int64_t BT, int C, const void* zero_page,
-            FinalFold* fin = nullptr) {
+            FinalFold* fin = nullptr, UsFold* usf = nullptr) {
     typedef GemmCfg<T> Gc;
     if constexpr (std::is_same<T, float>::value) {
 #ifndef ALSEP_F16_TU
         if (L.split) return run_tdf_split(ctx, L, X, Y, R, BT, C);
 #endif
     } else {
-        if (L.dma_path) return run_tdf_dma(ctx, L, X, Y, R, (const T*)zero_page, BT, C, fin);
+        if (L.dma_path) return run_tdf_dma(ctx, L, X, Y, R, (const T*)zero_page, BT, C, fin, usf);
     }
     const int64_t nunits = BT * (C / 16);
     const int64_t gx = ceil_div64(nunits, 8);
@@ -3528,10 +3709,11 @@ int run_tdf_fused(alsep_ctx* ctx, const Block& blk, const bf16_t* X, bf16_t* Y, 
 }
 
 // TFC_TDF block: cur -> dest, using scratch a, b (cur may alias b), hidden h.  fin (last block of the network only): the
-// residual TDF launch may produce the network's output instead of dest (FinalFold).
+// residual TDF launch may produce the network's output instead of dest (FinalFold).  usf (the block under the last upsampling only):
+// that launch may write the upsampled level-0 activation into dest instead of the block's output (UsFold; usf->out == dest).
 template <typename T>
 int run_block(alsep_ctx* ctx, const alsep_net* net, const Block& blk, const T* cur, T* a, T* b, T* h, T* dest,
-              int64_t B, int Th, int Fw, int c, FinalFold* fin = nullptr) {
+              int64_t B, int Th, int Fw, int c, FinalFold* fin = nullptr, UsFold* usf = nullptr) {
     const T* src = cur;
     T* pp[2] = {a, b};
     int rc;
@@ -3547,7 +3729,7 @@ int run_block(alsep_ctx* ctx, const alsep_net* net, const Block& blk, const T* c
             if ((rc = run_tdf_fused(ctx, blk, src, dest, B * Th, c, &fused)) || fused) return rc;
         }
         if ((rc = run_tdf<T>(ctx, blk.tdf[0], src, h, (const T*)nullptr, B * Th, c, net->zero_page.p))) return rc;
-        return run_tdf<T>(ctx, blk.tdf[1], h, dest, src, B * Th, c, net->zero_page.p, fin);
+        return run_tdf<T>(ctx, blk.tdf[1], h, dest, src, B * Th, c, net->zero_page.p, fin, usf);
     }
     return run_tdf<T>(ctx, blk.tdf[0], src, dest, src, B * Th, c, net->zero_page.p, fin);
 }
@@ -3615,6 +3797,20 @@ int forward_impl(alsep_ctx* ctx, const alsep_net* net, const T* in, T* out, int6
     // the last block may write `out` itself; the accumulating pass of a denoise pair (out_beta != 0) keeps the separate kernel
     FinalFold fold = {(const float*)net->final_w.p, (const float*)net->final_b.p, out, out_alpha, false};
     FinalFold* const fin = (!std::is_same<T, float>::value && out_beta == 0.f) ? &fold : nullptr;
+    // the block under the last upsampling may write the upsampled level-0 activation itself (UsFold), offered exactly where run_pix
+    // would launch us_stream_kernel<96, 48> for that layer
+    UsFold ufold = {};
+    UsFold* usf = nullptr;
+    if constexpr (!std::is_same<T, float>::value) {
+        if (net->n >= 1) {
+            const GemmLayer& U = net->us[net->n - 1];
+            const int Fp = cfg.dim_f / 2;
+            if (U.wfrag.p && U.K == 2 * TdfPersist::UC && U.M == 4 * TdfPersist::UC && switches().pix_stream && Fp % 64 == 0) {
+                ufold = {&U, ws + L.skip[0], nullptr, B * (cfg.dim_t / 2), Fp, false};
+                usf = &ufold;
+            }
+        }
+    }
     // rotating buffers: cur = P[ic]; the block uses the other two as scratch
     int ic = 0;
     for (int i = 0; i < net->n; ++i) {
@@ -3627,20 +3823,28 @@ int forward_impl(alsep_ctx* ctx, const alsep_net* net, const T* in, T* out, int6
     }
     {
         T* dest = P[(ic + 1) % 3];
-        if ((rc = run_block<T>(ctx, net, net->bott, P[ic], P[(ic + 2) % 3], P[ic], H, dest, B, Th, Fw, c, net->n == 0 ? fin : nullptr)))
+        UsFold* const uf = net->n == 1 ? usf : nullptr;
+        if (uf) uf->out = dest;
+        if ((rc = run_block<T>(ctx, net, net->bott, P[ic], P[(ic + 2) % 3], P[ic], H, dest, B, Th, Fw, c, net->n == 0 ? fin : nullptr, uf)))
             return rc;
         ic = (ic + 1) % 3;
     }
     for (int i = 0; i < net->n; ++i) {
         const T* skip = (const T*)(ws + L.skip[net->n - 1 - i]);
         const int c2 = c - cfg.g;
-        T* up = P[(ic + 1) % 3];
+        // a folded upsampling (the last one only) has left its result where the block's output would be: P[ic] is `up` already
+        const bool folded = i == net->n - 1 && ufold.done;
+        const int iu = folded ? ic : (ic + 1) % 3, id = folded ? (ic + 1) % 3 : ic;
+        T* up = P[iu];
         // us: P[ic] [B,Th,Fw,c] -> up [B,2Th,2Fw,c2] * skip
-        if ((rc = run_pix<T, PIX_US>(ctx, net->us[i], P[ic], up, skip, B * Th * Fw, Th, Fw, c, c2))) return rc;
+        if (!folded && (rc = run_pix<T, PIX_US>(ctx, net->us[i], P[ic], up, skip, B * Th * Fw, Th, Fw, c, c2))) return rc;
         Th *= 2; Fw *= 2; c = c2;
-        T* dest = P[ic];                                   // old input is dead after the up conv
-        if ((rc = run_block<T>(ctx, net, net->dec[i], up, P[(ic + 2) % 3], up, H, dest, B, Th, Fw, c, i == net->n - 1 ? fin : nullptr)))
+        T* dest = P[id];                                   // old input is dead after the up conv
+        UsFold* const uf = i == net->n - 2 ? usf : nullptr;
+        if (uf) uf->out = dest;
+        if ((rc = run_block<T>(ctx, net, net->dec[i], up, P[(ic + 2) % 3], up, H, dest, B, Th, Fw, c, i == net->n - 1 ? fin : nullptr, uf)))
             return rc;
+        ic = id;                                           // the block's output (unchanged unless the upsampling was folded)
     }
     if (fold.done) return ALSEP_OK;
     ProfScope prof(ctx, ALSEP_PROF_POINTWISE);
